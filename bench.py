@@ -167,6 +167,37 @@ def secondary_fp32(dev, with_oracle, steps=10):
     return out
 
 
+DUMP_SAMPLE = 1 << 21          # parameter elements drawn for the sample (with replacement, then deduplicated): about 2 M
+
+
+def dump_outputs(path, net, loss):
+    """What the caller of the train step holds after the last timed step, as float32 / float64 .npy files under ``path``: the loss,
+    the updated parameters and their gradients (one fixed, seeded sample of the flattened parameter list, its flat indices in
+    ``param_index``; all of it when the model is small) and every buffer (BatchNorm running statistics).  About 32 MB in all."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    params = list(net.parameters())
+    flat = torch.cat([p.detach().reshape(-1).float() for p in params])
+    grads = torch.cat([(p.grad.detach().reshape(-1).float() if p.grad is not None else torch.full((p.numel(),), float('nan'), device=flat.device))
+                       for p in params])
+    n = flat.numel()
+    if n > DUMP_SAMPLE:
+        idx = np.unique(np.random.default_rng(20220504).integers(0, n, DUMP_SAMPLE))
+        sel = torch.from_numpy(idx).to(flat.device)
+        flat, grads = flat[sel], grads[sel]
+    else:
+        idx = np.arange(n)
+    bufs = [b.detach().reshape(-1).double() for b in net.buffers()]
+    out = {'loss': np.array([float(loss)], dtype=np.float64),
+           'params': flat.cpu().numpy().astype(np.float32),
+           'grads': grads.cpu().numpy().astype(np.float32),
+           'param_index': idx.astype(np.float64),
+           'buffers': torch.cat(bufs).cpu().numpy() if bufs else np.zeros(0, dtype=np.float64)}
+    for name, a in out.items():
+        np.save(os.path.join(path, f'{name}.npy'), a)
+    return {'dir': path, 'arrays': {k: list(v.shape) for k, v in out.items()}, 'param_elements': n}
+
+
 def spawn_ranks(n):
     """Re-launch this script as ``n`` ranks under torch.distributed.run.  Runs in a parent that has not touched the GPU
     (importing torch does not initialise HIP; nothing here asks for a device).  Returns the launcher's exit status."""
@@ -260,7 +291,15 @@ def main():
                     help='dtype of the gradient buckets on the wire for --gpus N > 1: fp32 is what the reference\'s DataParallel reduces (default); '
                          'bf16 halves the bytes over xGMI (recorded in config.grad_wire_dtype)')
     ap.add_argument('--no-secondary', action='store_true', help='skip the Faster R-CNN (BASELINE config 5) block of the default one-GPU line')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed (loss, sampled parameters and gradients, BatchNorm buffers) as DIR/<name>.npy; '
+                         'the training state is reset to the state after the warm-up steps before the timed region, so equal arguments give '
+                         'equal inputs to every step of it')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    if args.dump_outputs is not None and (args.dry_run or args.model != 'yolov3'):
+        ap.error('--dump-outputs: only the YOLOv3 train step (--model yolov3, no --dry-run) writes its outputs')
     if args.gpus > 1 and 'RANK' not in os.environ and int(os.environ.get('WORLD_SIZE', '1')) <= 1:
         sys.exit(spawn_ranks(args.gpus))
     if args.dry_run:
@@ -268,7 +307,7 @@ def main():
     if args.model == 'faster_rcnn':
         sys.path.insert(0, os.path.join(ROOT, 'tools'))
         import bench_faster
-        bench_faster.main(steps=min(args.steps, 20), warmup=args.warmup, cpu_baseline=not args.no_cpu_baseline)
+        bench_faster.main(steps=args.steps, warmup=args.warmup, cpu_baseline=not args.no_cpu_baseline)
         return
 
     import torch.distributed as dist
@@ -350,6 +389,10 @@ def main():
         else:
             step()
     fence()
+    # --dump-outputs: how many untimed steps run from here to the timed region depends on the box (side-stream and graph
+    # autotuning, settle windows); the state after the warm-up is put back right before the timed region
+    from fastvision_amd.graphs import restore_train_state, snapshot_train_state
+    dump_snap = snapshot_train_state(net, opt) if args.dump_outputs is not None else None
     # untimed probe for the informative `kernels` table: all three convolution classes bracketed with HIP events inside the
     # library, issued eagerly with the weight gradients on the launch stream like everything else, so that every launch has the
     # GPU to itself (exclusive durations).  In the product configuration the wgrad launches run on the library's low-priority
@@ -470,6 +513,10 @@ def main():
         if prev is not None and abs(w - prev) <= 0.05 * min(w, prev):
             break
         prev = w
+    if dump_snap is not None:
+        fence()
+        restore_train_state(net, opt, dump_snap)
+        del dump_snap
     # The dominant kernel is the implicit-GEMM convolution (igemm8_kernel / igemm_kernel: forward + dgrad instances = 2/3 of the
     # convolution time); its roofline figure is measured live with HIP events on its FORWARD launches -- the instances that run
     # alone on the device (dgrad and wgrad launches share the GPU in the product configuration, so their event-to-event
@@ -536,6 +583,7 @@ def main():
         elapsed = time.perf_counter() - t0
     gc.callbacks.remove(gc_watch)
     final_loss = float(loss.detach())
+    dumped = dump_outputs(args.dump_outputs, net, final_loss) if args.dump_outputs is not None and rank == 0 else None
     roof_how = 'every launch' if args.shapes else f'every {SAMPLE_STRIDE}th launch of the class over the timed region'
     if use_graph:
         # the same step captured with event-record nodes around every forward convolution launch, replayed right after the
@@ -654,6 +702,8 @@ def main():
                           'reserved_gb': round(ms1.get('reserved_bytes.all.current', 0) / 2 ** 30, 2),
                           'active_peak_gb': round(ms1.get('active_bytes.all.peak', 0) / 2 ** 30, 2)},
         }
+        if dumped is not None:
+            out['dump_outputs'] = dumped
         if args.shapes:
             for k, v in sorted(kt.by_shape().items(), key=lambda kv: -kv[1][1]):
                 print(f'{k}: launches {v[0]} ms_total {v[1]:.3f} tflops {v[2]:.1f}', file=sys.stderr)

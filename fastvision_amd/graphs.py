@@ -39,6 +39,46 @@ def graphed_eval(model, example_images):
     return GraphedCallable(lambda im: model(im), example_images)
 
 
+def snapshot_train_state(model, optimizer):
+    """A device copy of what a training step changes: parameters, buffers (BatchNorm statistics), Adam moments and step counts."""
+    opt = optimizer
+    params = [p for g in opt.param_groups for p in g['params']]
+    started = [p for p in params if opt.state.get(p)]
+    return {'params': [p.detach().clone() for p in params], 'bufs': [b.detach().clone() for b in model.buffers()],
+            'moments': {p: (opt.state[p]['exp_avg'].clone(), opt.state[p]['exp_avg_sq'].clone(), opt._step_of(p)) for p in started},
+            'dev': {gi: d['state'].clone() for gi, d in opt._dev.items()}}
+
+
+def restore_train_state(model, optimizer, snap):
+    """Put back what ``snapshot_train_state`` copied, in place: the tensors keep their addresses (captured graphs stay valid) and
+    their version counters advance (packed-weight caches are rebuilt)."""
+    opt = optimizer
+    params = [p for g in opt.param_groups for p in g['params']]
+    with torch.no_grad():
+        for p, v in zip(params, snap['params']):
+            p.copy_(v)
+        for b, v in zip(model.buffers(), snap['bufs']):
+            b.copy_(v)
+        for p in params:
+            st = opt.state.get(p)
+            if not st:
+                continue
+            if p in snap['moments']:
+                m, v, k = snap['moments'][p]
+                st['exp_avg'].copy_(m)
+                st['exp_avg_sq'].copy_(v)
+                st['step'] = k
+            else:                                   # state born after the snapshot: back to a fresh optimizer's zeros
+                st['exp_avg'].zero_()
+                st['exp_avg_sq'].zero_()
+                st['step'] = 0
+        for gi, d in opt._dev.items():
+            if gi in snap['dev']:
+                d['state'].copy_(snap['dev'][gi])
+            else:
+                d['state'].zero_()
+
+
 class GraphedTrainStep:
     """The reference's per-batch training step (utils/fit.py:52-66: forward, zero_grad, loss, backward, optimizer step) captured
     ONCE in a HIP graph and replayed with one launch per batch.
@@ -135,38 +175,10 @@ class GraphedTrainStep:
         return loss.detach()
 
     def _snapshot(self):
-        opt = self.optimizer
-        bufs = [b for b in self.model.buffers()]
-        started = [p for p in self.params if opt.state.get(p)]
-        return {'params': [p.detach().clone() for p in self.params], 'bufs': [b.detach().clone() for b in bufs],
-                'moments': {p: (opt.state[p]['exp_avg'].clone(), opt.state[p]['exp_avg_sq'].clone(), opt._step_of(p)) for p in started},
-                'dev': {gi: d['state'].clone() for gi, d in opt._dev.items()}}
+        return snapshot_train_state(self.model, self.optimizer)
 
     def _restore(self, snap):
-        opt = self.optimizer
-        with torch.no_grad():
-            for p, v in zip(self.params, snap['params']):
-                p.copy_(v)
-            for b, v in zip(self.model.buffers(), snap['bufs']):
-                b.copy_(v)
-            for p in self.params:
-                st = opt.state.get(p)
-                if not st:
-                    continue
-                if p in snap['moments']:
-                    m, v, k = snap['moments'][p]
-                    st['exp_avg'].copy_(m)
-                    st['exp_avg_sq'].copy_(v)
-                    st['step'] = k
-                else:                                   # state born in the warm-up: back to a fresh optimizer's zeros
-                    st['exp_avg'].zero_()
-                    st['exp_avg_sq'].zero_()
-                    st['step'] = 0
-            for gi, d in opt._dev.items():
-                if gi in snap['dev']:
-                    d['state'].copy_(snap['dev'][gi])
-                else:
-                    d['state'].zero_()
+        restore_train_state(self.model, self.optimizer, snap)
 
     def __call__(self, images=None, targets=None):
         if images is not None:

@@ -76,7 +76,7 @@ print('ok')
     assert r.returncode == 0 and r.stdout.strip().endswith('ok'), r.stdout + r.stderr
 
 
-def test_anchor_generator_recovers_planted_clusters():
+def test_anchor_generator_recovers_planted_clusters(tmp_path):
     from fastvision_amd.detection.tools import AnchorGenerator
     rng = np.random.RandomState(3)
     centres = np.array([[0.05, 0.08], [0.2, 0.15], [0.5, 0.6]])
@@ -84,10 +84,10 @@ def test_anchor_generator_recovers_planted_clusters():
     labels = torch.from_numpy(np.concatenate([np.zeros((600, 4), np.float32), wh], axis=1))
     loader = [(torch.zeros(2, 3, 320, 640), labels[:300]), (torch.zeros(2, 3, 320, 640), labels[300:])]
     np.random.seed(0)
-    got = AnchorGenerator([loader], k=3, iters=30, cache='/tmp/fva_anchor_test').get_anchors()
+    got = AnchorGenerator([loader], k=3, iters=30, cache=str(tmp_path / 'anchors')).get_anchors()
     want = centres[::-1] * np.array([640, 320])                       # largest area first, input pixels
     assert got.shape == (3, 2) and np.allclose(got, want, rtol=0.05)
-    again = AnchorGenerator([loader], k=3, cache='/tmp/fva_anchor_test', use_cache=True).get_anchors()
+    again = AnchorGenerator([loader], k=3, cache=str(tmp_path / 'anchors'), use_cache=True).get_anchors()
     assert np.allclose(again, got)
 
 
