@@ -4,6 +4,11 @@
 //
 // Replaces torch.optim.Adam(..., betas=(0.937, 0.999), weight_decay=5e-4).step() as built by the reference
 // (demos/yolov3_u/train.py:66-70).
+//
+// Multi-tensor SGD (torch.optim.SGD, single-tensor path of torch/optim/sgd.py) with the Faster R-CNN demo's global-norm clipping
+// (demos/faster_rcnn/cfg/_fit.py:6-17) on the device: grad_sqnorm_partial -> clip_coef -> sgd_kernel.  The work is split into
+// fixed-size chunks of SGD_CHUNK elements (one block per chunk, host-built chunk table), not into tensors, so one 103 M-element
+// tensor (VGG fc6) spreads over every CU instead of over blockIdx.x of one tensor.
 #include <math.h>
 
 #include "common.h"
@@ -78,6 +83,138 @@ __global__ __launch_bounds__(256) void gather_cast_kernel(const int64_t* __restr
     }
 }
 
+
+// ---- SGD --------------------------------------------------------------------------------------------------------------------
+// tab: int64 [6][n] = param | grad | momentum buffer (0: none) | element count | group index | slot in the fresh-flag array.
+// chunks: int64 [nchunks] = (tensor << 32) | chunk number; the chunk covers elements [c * SGD_CHUNK, min((c + 1) * SGD_CHUNK, size)).
+// hyper: float [G][SGD_HYPER] = lr, weight decay, momentum, 1 - dampening, nesterov (0 / 1), one row per parameter group.
+// fresh: int32 per slot; non-zero = the momentum buffer has no history yet (torch's `buf = clone(grad)`).
+constexpr int SGD_CHUNK = 16384;        // 64 KiB of fp32 per block: 16 float4 iterations of 256 threads
+constexpr int SGD_THREADS = 256;
+constexpr int SGD_HYPER = 5;
+
+struct SgdChunk {
+    int64_t t, begin, end;
+};
+__device__ __forceinline__ SgdChunk sgd_chunk(const int64_t* __restrict__ tab, int n, const int64_t* __restrict__ chunks) {
+    const int64_t e = chunks[blockIdx.x];
+    SgdChunk c;
+    c.t = e >> 32;
+    c.begin = (e & 0xffffffffll) * SGD_CHUNK;
+    const int64_t size = tab[3 * n + c.t];
+    c.end = c.begin + SGD_CHUNK < size ? c.begin + SGD_CHUNK : size;
+    return c;
+}
+
+// fixed-order block sum of one double per thread (wave64 butterfly, then the four waves in order): bit-identical from run to run
+__device__ __forceinline__ double block_sum(double v, double* lds) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
+    __syncthreads();
+    double s = 0.0;
+    if (threadIdx.x == 0)
+        for (int w = 0; w < SGD_THREADS / 64; ++w) s += lds[w];
+    return s;        // valid in thread 0
+}
+
+// partial[chunk] = sum of grad^2 over the chunk, accumulated in fp64 (no atomics: one slot per chunk)
+__global__ __launch_bounds__(SGD_THREADS) void grad_sqnorm_partial(const int64_t* __restrict__ tab, int n, const int64_t* __restrict__ chunks,
+                                                                  double* __restrict__ partial) {
+    __shared__ double lds[SGD_THREADS / 64];
+    const SgdChunk c = sgd_chunk(tab, n, chunks);
+    const float* __restrict__ g = (const float*)tab[n + c.t];
+    double acc = 0.0;
+    int64_t i = c.begin;
+    if (((uintptr_t)g & 15) == 0) {
+        const int64_t vend = c.begin + ((c.end - c.begin) & ~(int64_t)3);
+        for (int64_t j = c.begin + 4 * (int64_t)threadIdx.x; j < vend; j += 4 * SGD_THREADS) {
+            const f32x4 v = *(const f32x4*)(g + j);
+            acc += (double)v[0] * v[0] + (double)v[1] * v[1] + (double)v[2] * v[2] + (double)v[3] * v[3];
+        }
+        i = vend;
+    }
+    for (int64_t j = i + threadIdx.x; j < c.end; j += SGD_THREADS) acc += (double)g[j] * g[j];
+    const double s = block_sum(acc, lds);
+    if (threadIdx.x == 0) partial[blockIdx.x] = s;
+}
+
+// out[0] = norm = sqrt(sum of the partials, in chunk order) as fp32; out[1] = clip / max(norm, clip) as the reference's Python
+// computes it (float norm -> double, Python's max keeps its first argument unless the second is larger: max(nan, c) = nan)
+__global__ __launch_bounds__(SGD_THREADS) void clip_coef(const double* __restrict__ partial, int nchunks, double clip, float* __restrict__ out) {
+    __shared__ double lds[SGD_THREADS / 64];
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < nchunks; i += SGD_THREADS) acc += partial[i];
+    const double s = block_sum(acc, lds);
+    if (threadIdx.x == 0) {
+        const float norm = (float)sqrt(s);
+        const double nd = (double)norm;
+        const double m = clip > nd ? clip : nd;
+        out[0] = norm;
+        out[1] = (float)(clip / m);      // inf norm -> 0, nan norm -> nan
+    }
+}
+
+struct SgdHyper {
+    float lr, wd, momentum, keep, nesterov;      // keep = 1 - dampening
+};
+
+// torch's update order: g = coef * grad; g += wd * p; buf = g (first step) or momentum * buf + (1 - dampening) * g;
+// g = g + momentum * buf (Nesterov) or buf; p -= lr * g
+__device__ __forceinline__ void sgd_one(float& p, float gr, float& b, const SgdHyper& h, float coef, bool mom, bool first) {
+    float g = coef * gr;
+    if (h.wd != 0.f) g = g + h.wd * p;
+    if (mom) {
+        b = first ? g : h.momentum * b + h.keep * g;
+        g = h.nesterov != 0.f ? g + h.momentum * b : b;
+    }
+    p = p - h.lr * g;
+}
+
+__global__ __launch_bounds__(SGD_THREADS) void sgd_kernel(const int64_t* __restrict__ tab, int n, const int64_t* __restrict__ chunks,
+                                                          const float* __restrict__ hyper, const int32_t* __restrict__ fresh,
+                                                          const float* __restrict__ coef_dev) {
+    const SgdChunk c = sgd_chunk(tab, n, chunks);
+    float* __restrict__ p = (float*)tab[c.t];
+    const float* __restrict__ g = (const float*)tab[n + c.t];
+    float* __restrict__ b = (float*)tab[2 * n + c.t];
+    const float* hp = hyper + tab[4 * n + c.t] * SGD_HYPER;
+    const SgdHyper h{hp[0], hp[1], hp[2], hp[3], hp[4]};
+    const float coef = coef_dev ? *coef_dev : 1.f;
+    const bool mom = b != nullptr;
+    const bool first = mom && fresh[tab[5 * n + c.t]] != 0;
+    float dummy = 0.f;
+    int64_t i = c.begin;
+    if ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)b) & 15) == 0) {
+        const int64_t vend = c.begin + ((c.end - c.begin) & ~(int64_t)3);
+        for (int64_t j = c.begin + 4 * (int64_t)threadIdx.x; j < vend; j += 4 * SGD_THREADS) {
+            f32x4 pv = *(f32x4*)(p + j);
+            const f32x4 gv = *(const f32x4*)(g + j);
+            f32x4 bv = mom ? *(f32x4*)(b + j) : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                float pk = pv[k], bk = bv[k];
+                sgd_one(pk, gv[k], bk, h, coef, mom, first);
+                pv[k] = pk;
+                bv[k] = bk;
+            }
+            *(f32x4*)(p + j) = pv;
+            if (mom) *(f32x4*)(b + j) = bv;
+        }
+        i = vend;
+    }
+    for (int64_t j = i + threadIdx.x; j < c.end; j += SGD_THREADS) {
+        float pk = p[j];
+        float& bk = mom ? b[j] : dummy;
+        sgd_one(pk, g[j], bk, h, coef, mom, first);
+        p[j] = pk;
+    }
+}
+
+// after an update that initialised buffers: their history starts now
+__global__ void sgd_clear_fresh(const int64_t* __restrict__ tab, int n, int32_t* __restrict__ fresh) {
+    for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < n; t += gridDim.x * blockDim.x) fresh[tab[5 * n + t]] = 0;
+}
+
 }  // namespace
 
 extern "C" int fva_gather_cast(const int64_t* table_dev, int32_t n, int64_t max_size, void* dst, int dst_dtype, void* stream) {
@@ -117,5 +254,33 @@ extern "C" int fva_adam_step_dev(const void* const* ptrs, const int64_t* sizes, 
     hipLaunchKernelGGL(adam_kernel, dim3((int)gx, n), dim3(256), 0, (hipStream_t)stream, ptrs, sizes, n, 0.f, 1.f, beta1, beta2, eps,
                        weight_decay, grad_scale, (const double*)state_dev);
     FVA_LAUNCH_CHECK("adam_kernel");
+    return FVA_OK;
+}
+
+extern "C" int fva_sgd_chunk_elems(void) { return SGD_CHUNK; }
+
+extern "C" int fva_sgd_clip_coef(const int64_t* tab_dev, int32_t n, const int64_t* chunks_dev, int32_t nchunks, double* partial_dev,
+                                 double clip_norm, float* out_dev, void* stream) {
+    if (!tab_dev || n < 1 || !chunks_dev || nchunks < 1 || !partial_dev || !out_dev)
+        return fva_fail(FVA_ERR_ARG, "fva_sgd_clip_coef: bad argument (null table / buffer or empty chunk list)");
+    if (!(clip_norm > 0.0) || isinf(clip_norm)) return fva_fail(FVA_ERR_ARG, "fva_sgd_clip_coef: clip_norm must be finite and > 0 (got %g)", clip_norm);
+    hipLaunchKernelGGL(grad_sqnorm_partial, dim3(nchunks), dim3(SGD_THREADS), 0, (hipStream_t)stream, tab_dev, n, chunks_dev, partial_dev);
+    FVA_LAUNCH_CHECK("grad_sqnorm_partial");
+    hipLaunchKernelGGL(clip_coef, dim3(1), dim3(SGD_THREADS), 0, (hipStream_t)stream, (const double*)partial_dev, nchunks, clip_norm, out_dev);
+    FVA_LAUNCH_CHECK("clip_coef");
+    return FVA_OK;
+}
+
+extern "C" int fva_sgd_step(const int64_t* tab_dev, int32_t n, const int64_t* chunks_dev, int32_t nchunks, const float* hyper_dev,
+                            int32_t* fresh_dev, int32_t clear_fresh, const float* coef_dev, void* stream) {
+    if (!tab_dev || n < 1 || !chunks_dev || nchunks < 1 || !hyper_dev || !fresh_dev)
+        return fva_fail(FVA_ERR_ARG, "fva_sgd_step: bad argument (null table / hyper-parameters / fresh flags or empty chunk list)");
+    hipLaunchKernelGGL(sgd_kernel, dim3(nchunks), dim3(SGD_THREADS), 0, (hipStream_t)stream, tab_dev, n, chunks_dev, hyper_dev,
+                       (const int32_t*)fresh_dev, coef_dev);
+    FVA_LAUNCH_CHECK("sgd_kernel");
+    if (clear_fresh) {
+        hipLaunchKernelGGL(sgd_clear_fresh, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, tab_dev, n, fresh_dev);
+        FVA_LAUNCH_CHECK("sgd_clear_fresh");
+    }
     return FVA_OK;
 }

@@ -4,7 +4,9 @@ Step contract (_fit.py:35-50): losses = model(images, targets); optimizer.zero_g
 loss.backward(); clip_gradient(model, 10.) ("for vgg only"); optimizer.step(); the learning rate is divided by ten at every ninth
 epoch (:22-24) and the model's state_dict is saved after each epoch (:30).  Differences: the batch goes to the GPU here (the
 reference leaves its .cuda() calls commented out and relies on DataParallel), the global norm is computed on the device with one
-read-back instead of one per parameter, and the per-batch print reads the five loss values back in one transfer.
+read-back instead of one per parameter, and the per-batch print reads the five loss values back in one transfer.  An optimizer
+that clips by itself (``clip_norm`` set, e.g. fastvision_amd.FusedSGD(..., clip_norm=10.): norm and coefficient on the device, no
+read-back) replaces the clip_gradient call.
 """
 import torch
 
@@ -33,7 +35,8 @@ def _Train(model, train_loader, optimizer, log=print):
         parts = torch.stack([l.reshape(()) for l in (loss_rpn_cls, loss_rpn_box, loss_fast_cls, loss_fast_box)])
         loss = parts.sum()
         loss.backward()
-        clip_gradient(model, CLIP_NORM)
+        if getattr(optimizer, 'clip_norm', None) is None:
+            clip_gradient(model, CLIP_NORM)
         optimizer.step()
         if log:
             log(*torch.cat([loss.detach().reshape(1), parts.detach()]).tolist())

@@ -5,7 +5,7 @@ eager loop is host-bound.  ``GraphedCallable`` runs the callable once under ``to
 C ABI only launches kernels on the current stream, which is the capture stream) and afterwards replays the whole sequence
 with one launch.  Inputs are copied into the captured buffers; outputs are the captured tensors (consume or clone them
 before the next call).  ``GraphedTrainStep`` captures the whole training step: its Adam step count and learning rate live on the
-device (FusedAdam(capturable=True)) and its target table has a fixed capacity.
+device (FusedAdam(capturable=True) or FusedSGD(capturable=True)) and its target table has a fixed capacity.
 """
 import torch
 
@@ -40,43 +40,23 @@ def graphed_eval(model, example_images):
 
 
 def snapshot_train_state(model, optimizer):
-    """A device copy of what a training step changes: parameters, buffers (BatchNorm statistics), Adam moments and step counts."""
-    opt = optimizer
-    params = [p for g in opt.param_groups for p in g['params']]
-    started = [p for p in params if opt.state.get(p)]
+    """A device copy of what a training step changes: parameters, buffers (BatchNorm statistics) and the optimizer's state (Adam
+    moments and step counts, SGD momentum buffers: ``optimizer.snapshot_state()``)."""
+    params = [p for g in optimizer.param_groups for p in g['params']]
     return {'params': [p.detach().clone() for p in params], 'bufs': [b.detach().clone() for b in model.buffers()],
-            'moments': {p: (opt.state[p]['exp_avg'].clone(), opt.state[p]['exp_avg_sq'].clone(), opt._step_of(p)) for p in started},
-            'dev': {gi: d['state'].clone() for gi, d in opt._dev.items()}}
+            'optimizer': optimizer.snapshot_state()}
 
 
 def restore_train_state(model, optimizer, snap):
     """Put back what ``snapshot_train_state`` copied, in place: the tensors keep their addresses (captured graphs stay valid) and
     their version counters advance (packed-weight caches are rebuilt)."""
-    opt = optimizer
-    params = [p for g in opt.param_groups for p in g['params']]
+    params = [p for g in optimizer.param_groups for p in g['params']]
     with torch.no_grad():
         for p, v in zip(params, snap['params']):
             p.copy_(v)
         for b, v in zip(model.buffers(), snap['bufs']):
             b.copy_(v)
-        for p in params:
-            st = opt.state.get(p)
-            if not st:
-                continue
-            if p in snap['moments']:
-                m, v, k = snap['moments'][p]
-                st['exp_avg'].copy_(m)
-                st['exp_avg_sq'].copy_(v)
-                st['step'] = k
-            else:                                   # state born after the snapshot: back to a fresh optimizer's zeros
-                st['exp_avg'].zero_()
-                st['exp_avg_sq'].zero_()
-                st['step'] = 0
-        for gi, d in opt._dev.items():
-            if gi in snap['dev']:
-                d['state'].copy_(snap['dev'][gi])
-            else:
-                d['state'].zero_()
+        optimizer.restore_state(snap['optimizer'])
 
 
 class GraphedTrainStep:
@@ -86,7 +66,8 @@ class GraphedTrainStep:
     Eager, a YOLOv3 step is ~900 C-ABI calls issued from Python (15-23 ms of host time for ~31 ms of GPU work at B=32, 640 px);
     replayed, the host needs ~0.1 ms and the kernels run back to back.  What used to be host scalars lives on the device:
       * the Adam step count and learning rate (FusedAdam(capturable=True): fva_adam_step_dev; an LR scheduler may keep rewriting
-        ``param_groups[i]['lr']`` -- the wrapper refreshes the device scalar before each replay);
+        ``param_groups[i]['lr']`` -- the wrapper refreshes the device scalar before each replay), or the SGD hyper-parameter table,
+        clipping scalars and momentum-buffer initialisation flags (FusedSGD(capturable=True): fva_sgd_step);
       * the target table: a fixed-capacity [max_targets, 6] buffer whose unused rows are zero.  A zero-size box matches no anchor
         (loss/yolov3_loss.py:98-99: max(r, 1/r) = inf), so the library loss sees exactly the rows the reference would; the demo
         loss assigns EVERY row to its best anchor, so it must be captured with its exact target count (max_targets=None).
@@ -110,7 +91,8 @@ class GraphedTrainStep:
     def __init__(self, model, loss_fn, optimizer, images, targets, max_targets=None, warmup=2, pre_step=None, on_capture=None,
                  side_stream=False):
         if not getattr(optimizer, 'capturable', False):
-            raise RuntimeError('GraphedTrainStep needs FusedAdam(..., capturable=True): step count and LR must live on the device')
+            raise RuntimeError('GraphedTrainStep needs FusedAdam(..., capturable=True) or FusedSGD(..., capturable=True): '
+                               'step count and LR must live on the device')
         if not model.training:
             raise RuntimeError('GraphedTrainStep: put the model in train mode first')
         self.model, self.loss_fn, self.optimizer, self.pre_step = model, loss_fn, optimizer, pre_step
@@ -149,7 +131,7 @@ class GraphedTrainStep:
             self._restore(snap)
             optimizer.zero_grad(set_to_none=True)
             torch.autograd.graph.increment_version(self.params)      # the captured sequence must start with the weight re-pack
-            steps_before = [optimizer._step_of(p) if optimizer.state.get(p) else None for p in self.params]
+            host_before = optimizer.host_state()                    # e.g. Adam's step counts
             self._adam_staging = optimizer.begin_capture()           # this graph's own pointer-table words (kept alive with it)
             if on_capture is not None:
                 on_capture()                                         # e.g. arm the library's event spans: they become graph nodes
@@ -158,9 +140,7 @@ class GraphedTrainStep:
                 self.loss = self._step()
         finally:
             ops.set_wgrad_side_stream(side_was)
-        for p, st in zip(self.params, steps_before):                 # capture ran the host side of optimizer.step() once
-            if st is not None:
-                optimizer.state[p]['step'] = st
+        optimizer.set_host_state(host_before)                        # capture ran the host side of optimizer.step() once
         torch.autograd.graph.increment_version(self.params)
         self.replays = 0
 

@@ -17,7 +17,7 @@ import torch
 from . import _lib
 from .ops import _stream
 
-__all__ = ['FusedAdam']
+__all__ = ['FusedAdam', 'FusedSGD']
 
 
 class FusedAdam(torch.optim.Optimizer):
@@ -129,6 +129,42 @@ class FusedAdam(torch.optim.Optimizer):
                 if st:
                     st['step'] = self._step_of(p) + k
 
+    # ---- graphs.GraphedTrainStep --------------------------------------------------------------------------------------
+    def snapshot_state(self):
+        """A device copy of the optimizer state a training step changes: moments, host step counts and device step counters."""
+        started = [p for g in self.param_groups for p in g['params'] if self.state.get(p)]
+        return {'moments': {p: (self.state[p]['exp_avg'].clone(), self.state[p]['exp_avg_sq'].clone(), self._step_of(p)) for p in started},
+                'dev': {gi: d['state'].clone() for gi, d in self._dev.items()}}
+
+    def restore_state(self, snap):
+        """Put back what ``snapshot_state`` copied, in place (the tensors keep their addresses: captured graphs stay valid)."""
+        for p in (p for g in self.param_groups for p in g['params']):
+            st = self.state.get(p)
+            if not st:
+                continue
+            if p in snap['moments']:
+                m, v, k = snap['moments'][p]
+                st['exp_avg'].copy_(m)
+                st['exp_avg_sq'].copy_(v)
+                st['step'] = k
+            else:                                   # state born after the snapshot: back to a fresh optimizer's zeros
+                st['exp_avg'].zero_()
+                st['exp_avg_sq'].zero_()
+                st['step'] = 0
+        for gi, d in self._dev.items():
+            if gi in snap['dev']:
+                d['state'].copy_(snap['dev'][gi])
+            else:
+                d['state'].zero_()
+
+    def host_state(self):
+        """What the host side of one ``step()`` changes (the step counts): saved before a capture, put back after it."""
+        return [(p, self._step_of(p)) for g in self.param_groups for p in g['params'] if self.state.get(p)]
+
+    def set_host_state(self, saved):
+        for p, k in saved:
+            self.state[p]['step'] = k
+
     @torch.no_grad()
     def step(self, closure=None):
         loss = None
@@ -158,4 +194,261 @@ class FusedAdam(torch.optim.Optimizer):
                 _lib.call('fva_adam_step', C.c_void_p(tab.data_ptr()), C.c_void_p(sizes.data_ptr()), n, mx, group['lr'], b1, b2,
                           group['eps'], group['weight_decay'], step, self.grad_scale, _stream())
             torch.autograd.graph.increment_version(ps)      # the kernel wrote p in place: invalidate packed-weight caches
+        return loss
+
+
+class FusedSGD(torch.optim.Optimizer):
+    """torch.optim.SGD semantics (the optimizer of the reference's Faster R-CNN demo, demos/faster_rcnn/train.py:91-109: momentum
+    0.937, Nesterov, parameter groups) as ONE multi-tensor HIP launch per step for every group (``fva_sgd_step``), with the demo's
+    gradient-norm clipping (cfg/_fit.py:6-17) optionally on the device.
+
+    Drop-in for ``torch.optim.SGD(params, lr, momentum, dampening, weight_decay, nesterov)``: same argument checks, same update
+    order (single-tensor path of torch/optim/sgd.py), same state (``state[p]['momentum_buffer']``, no entry when momentum is 0), so
+    ``state_dict()`` / ``load_state_dict()`` exchange checkpoints with torch's SGD in both directions.  Parameters whose ``.grad`` is
+    None are skipped as torch skips them: no buffer, nothing added to the norm (the reference's clip_gradient would fail on them).
+
+    ``clip_norm``: ``step()`` first computes the global L2 norm of all groups' gradients (``fva_sgd_clip_coef``: fp64 per chunk,
+    fixed order, no atomics) and the reference's coefficient ``clip_norm / max(norm, clip_norm)`` into device scalars, then the
+    update multiplies each gradient by it as it reads it.  Nothing is read back: no host synchronisation.  ``p.grad`` itself is NOT
+    rewritten (the reference scales it in place); ``last_grad_norm`` is the fp32 device scalar of the norm (overwritten by the next
+    step).  A non-finite norm behaves as the reference: NaN gives NaN parameters, infinity a coefficient of 0.
+
+    ``capturable=True`` follows FusedAdam's protocol for graphs.GraphedTrainStep: the hyper-parameters (lr of each group) live in a
+    device table that ``step()`` / ``sync_lr()`` refresh when ``param_groups`` change, ``begin_capture()`` gives each graph its own
+    pointer-table staging, and at least one eager ``step()`` must run before a capture.  Whether a momentum buffer still has to be
+    initialised is a device flag, so a captured step restored to a fresh optimizer's state initialises it exactly once.
+    Parameters and gradients must be contiguous fp32 tensors on the GPU (no CPU path).  ``lr`` defaults to 1e-3 as in torch's SGD;
+    ``maximize``, ``foreach``, ``fused`` and ``differentiable`` are accepted only at torch's defaults (False, None, None, False):
+    any other value, ``foreach=False`` included, is refused rather than silently ignored.
+    """
+
+    def __init__(self, params, lr=1e-3, momentum=0, dampening=0, weight_decay=0, nesterov=False, clip_norm=None, capturable=False,
+                 *, maximize=False, foreach=None, differentiable=False, fused=None):
+        if maximize is not False or differentiable is not False or foreach is not None or fused is not None:
+            raise ValueError('FusedSGD: maximize, foreach, fused and differentiable are not supported (it is its own fused kernel); '
+                             'leave them at their defaults (False, None, None, False)')
+        if torch.is_tensor(lr) and lr.numel() != 1:
+            raise ValueError('Tensor lr must be 1-element')
+        if lr < 0.0:
+            raise ValueError(f'Invalid learning rate: {lr}')
+        if momentum < 0.0:
+            raise ValueError(f'Invalid momentum value: {momentum}')
+        if weight_decay < 0.0:
+            raise ValueError(f'Invalid weight_decay value: {weight_decay}')
+        if nesterov and (momentum <= 0 or dampening != 0):
+            raise ValueError('Nesterov momentum requires a momentum and zero dampening')
+        if clip_norm is not None and not (0.0 < float(clip_norm) < float('inf')):
+            raise ValueError(f'Invalid clip_norm value: {clip_norm}')
+        super().__init__(params, dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov,
+                                      maximize=False, foreach=None, differentiable=False, fused=None))
+        self.clip_norm = None if clip_norm is None else float(clip_norm)
+        self.capturable = capturable
+        self._tab = None          # (key, table, n, host words) of the last pointer table
+        self._chunks = None       # (sizes, chunk table, nchunks, fp64 partials)
+        self._hyper = None        # (host values, device float [G][5])
+        self._fresh = None        # device int32 per parameter slot: the momentum buffer has no history yet
+        self._clip_out = None     # device float [2]: norm, coefficient
+        self._stage = None        # capturable: (pinned words, device table) re-read by a captured copy node
+
+    def __setstate__(self, state):
+        super().__setstate__(state)
+        for group in self.param_groups:
+            group.setdefault('nesterov', False)
+
+    # ---- checkpoints -------------------------------------------------------------------------------------------------
+    def load_state_dict(self, state_dict):
+        super().load_state_dict(state_dict)
+        self._tab = None                          # the buffers were replaced: the pointer table is stale
+        for p, st in self.state.items():          # a loaded buffer has history (torch's SGD continues it)
+            buf = st.get('momentum_buffer')
+            if buf is not None and not buf.is_contiguous():
+                st['momentum_buffer'] = buf.contiguous()
+        if self._fresh is not None:
+            self._fresh.zero_()
+
+    @property
+    def last_grad_norm(self):
+        """fp32 device scalar of the global gradient norm of the last clipped step (None before one)."""
+        return None if self._clip_out is None else self._clip_out[0]
+
+    # ---- tables ------------------------------------------------------------------------------------------------------
+    def _params(self):
+        return [p for g in self.param_groups for p in g['params']]
+
+    def _slots(self, dev):
+        allp = self._params()
+        if self._fresh is None or self._fresh.numel() < len(allp):
+            fresh = torch.zeros(len(allp), dtype=torch.int32, device=dev)
+            if self._fresh is not None:
+                fresh[:self._fresh.numel()].copy_(self._fresh)
+            self._fresh = fresh
+        return {p: i for i, p in enumerate(allp)}
+
+    def _sync_hyper(self, dev):
+        vals = []
+        for g in self.param_groups:
+            vals += [float(g['lr']), float(g['weight_decay']), float(g['momentum']), 1.0 - float(g['dampening']), 1.0 if g['nesterov'] else 0.0]
+        vals = tuple(vals)
+        if self._hyper is not None and self._hyper[0] == vals:
+            return
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError('FusedSGD: hyper-parameters changed during a graph capture; call sync_lr() before capturing')
+        host = torch.tensor(vals, dtype=torch.float32).pin_memory()
+        if self._hyper is not None and self._hyper[1].numel() == len(vals):
+            devt = self._hyper[1]
+        else:
+            devt = torch.empty(len(vals), dtype=torch.float32, device=dev)
+        devt.copy_(host, non_blocking=True)
+        self._hyper = (vals, devt, host)
+
+    def sync_lr(self):
+        """Refresh the device hyper-parameter table from param_groups (capturable mode; graphs.GraphedTrainStep calls it before each
+        replay, after an LR scheduler changed them).  One small asynchronous upload when something changed, no host sync."""
+        if self._hyper is not None:
+            self._sync_hyper(self._hyper[1].device)
+
+    def _chunk_table(self, sizes, dev):
+        if self._chunks is not None and self._chunks[0] == sizes:
+            return self._chunks
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError('FusedSGD: run at least one eager step() before capturing a graph')
+        per = _lib.call('fva_sgd_chunk_elems')
+        words = [(t << 32) | c for t, n in enumerate(sizes) for c in range((n + per - 1) // per)]
+        chunks = torch.tensor(words, dtype=torch.int64).pin_memory().to(dev, non_blocking=True)
+        partial = torch.empty(len(words), dtype=torch.float64, device=dev)
+        self._chunks = (sizes, chunks, len(words), partial)
+        return self._chunks
+
+    def _table(self):
+        """Device table [6][n] of the parameters that have a gradient (all groups), rebuilt only when a pointer moved."""
+        ps, gids = [], []
+        for gi, group in enumerate(self.param_groups):
+            for p in group['params']:
+                if p.grad is None:
+                    continue
+                if not p.is_cuda:
+                    raise RuntimeError('FusedSGD: parameters must live on the GPU (no CPU path)')
+                if p.dtype != torch.float32 or p.grad.dtype != torch.float32 or not p.is_contiguous() or not p.grad.is_contiguous():
+                    raise RuntimeError('FusedSGD needs contiguous fp32 parameters and gradients')
+                if p.grad.is_sparse:
+                    raise RuntimeError('FusedSGD does not support sparse gradients')
+                ps.append(p)
+                gids.append(gi)
+        if not ps:
+            return None
+        dev = ps[0].device
+        slots = self._slots(dev)
+        capturing = torch.cuda.is_current_stream_capturing()
+        born = []
+        for p, gi in zip(ps, gids):
+            if self.param_groups[gi]['momentum'] != 0 and self.state[p].get('momentum_buffer') is None:
+                if capturing:
+                    raise RuntimeError('FusedSGD: run at least one eager step() (capturable=True) and begin_capture() before capturing a graph')
+                self.state[p]['momentum_buffer'] = torch.empty_like(p, memory_format=torch.contiguous_format)
+                born.append(slots[p])
+        if born:                                  # their first update is torch's clone(grad)
+            idx = torch.tensor(born, dtype=torch.int64).pin_memory().to(dev, non_blocking=True)
+            self._fresh.index_fill_(0, idx, 1)
+        bufs = [self.state[p]['momentum_buffer'].data_ptr() if self.param_groups[gi]['momentum'] != 0 else 0 for p, gi in zip(ps, gids)]
+        key = (tuple(p.data_ptr() for p in ps), tuple(p.grad.data_ptr() for p in ps), tuple(bufs), tuple(gids))
+        sizes = tuple(p.numel() for p in ps)
+        chunks = self._chunk_table(sizes, dev)
+        if self._tab is None or self._tab[0] != key:
+            n = len(ps)
+            vals = list(key[0]) + list(key[1]) + list(key[2]) + list(sizes) + list(gids) + [slots[p] for p in ps]
+            if capturing:
+                # nothing may be allocated on the host during a capture: the staging words were made by an eager step; the captured
+                # copy node re-reads them on every replay
+                if self._stage is None or self._stage[0].numel() != len(vals):
+                    raise RuntimeError('FusedSGD: run at least one eager step() (capturable=True) and begin_capture() before capturing a graph')
+                host, tab = self._stage
+                host.copy_(torch.tensor(vals, dtype=torch.int64))
+                tab.copy_(host, non_blocking=True)
+            else:
+                host = torch.tensor(vals, dtype=torch.int64).pin_memory()
+                tab = host.to(dev, non_blocking=True)
+                if self.capturable and (self._stage is None or self._stage[0].numel() != len(vals)):
+                    self._stage = (torch.empty(len(vals), dtype=torch.int64).pin_memory(), torch.empty(len(vals), dtype=torch.int64, device=dev))
+            self._tab = (key, tab, n, host)
+        # the device flags are the only record of which buffers still need torch's clone(grad): every update that has momentum
+        # buffers clears the flags of its tensors afterwards (one tiny launch, idempotent), so eager steps, captured steps and
+        # replays after restore_state() all agree without any host-side bookkeeping
+        clear = any(b != 0 for b in bufs)
+        return ps, self._tab[1], self._tab[2], chunks, clear
+
+    def begin_capture(self):
+        """Fresh staging words for ONE graph capture (call right before ``torch.cuda.graph``, after a warm-up step); the graph's owner
+        keeps the returned buffers alive as long as the graph (see FusedAdam.begin_capture)."""
+        owned = []
+        if self._stage is not None:
+            n = self._stage[0].numel()
+            self._stage = (torch.empty(n, dtype=torch.int64).pin_memory(), torch.empty(n, dtype=torch.int64, device=self._stage[1].device))
+            owned.append(self._stage)
+        self._tab = None                  # the capture-time step must write (and record the upload of) its own table
+        return owned
+
+    # ---- graphs.GraphedTrainStep --------------------------------------------------------------------------------------
+    def snapshot_state(self):
+        """A device copy of the momentum buffers and their fresh flags."""
+        started = [p for p in self._params() if self.state.get(p, {}).get('momentum_buffer') is not None]
+        return {'bufs': {p: self.state[p]['momentum_buffer'].clone() for p in started},
+                'fresh': None if self._fresh is None else self._fresh.clone()}
+
+    def restore_state(self, snap):
+        """Put back what ``snapshot_state`` copied, in place.  A buffer born after the snapshot keeps its address and is flagged
+        fresh again: the next update initialises it as a new optimizer's first step would."""
+        if self._fresh is not None:
+            if snap['fresh'] is not None:
+                self._fresh[:snap['fresh'].numel()].copy_(snap['fresh'])
+            else:
+                self._fresh.zero_()
+        slots = self._slots(self._fresh.device) if self._fresh is not None else {}
+        born = []
+        for p in self._params():
+            buf = self.state.get(p, {}).get('momentum_buffer')
+            if buf is None:
+                continue
+            if p in snap['bufs']:
+                buf.copy_(snap['bufs'][p])
+            else:
+                buf.zero_()
+                born.append(slots[p])
+        if born:
+            self._fresh.index_fill_(0, torch.tensor(born, dtype=torch.int64, device=self._fresh.device), 1)
+
+    def host_state(self):
+        return None                       # the host side of step() keeps no counters
+
+    def set_host_state(self, saved):
+        pass
+
+    def note_replayed_steps(self, k=1):
+        pass
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        from .ops import join_side_stream
+        join_side_stream()          # weight gradients may still be in flight on the library's side stream
+        got = self._table()
+        if got is None:
+            return loss
+        ps, tab, n, (_, chunks, nchunks, partial), clear = got
+        dev = ps[0].device
+        self._sync_hyper(dev)
+        coef = C.c_void_p(0)
+        if self.clip_norm is not None:
+            if self._clip_out is None:
+                if torch.cuda.is_current_stream_capturing():
+                    raise RuntimeError('FusedSGD: run at least one eager step() before capturing a graph')
+                self._clip_out = torch.zeros(2, dtype=torch.float32, device=dev)
+            _lib.call('fva_sgd_clip_coef', C.c_void_p(tab.data_ptr()), n, C.c_void_p(chunks.data_ptr()), nchunks,
+                      C.c_void_p(partial.data_ptr()), self.clip_norm, C.c_void_p(self._clip_out.data_ptr()), _stream())
+            coef = C.c_void_p(self._clip_out.data_ptr() + 4)
+        _lib.call('fva_sgd_step', C.c_void_p(tab.data_ptr()), n, C.c_void_p(chunks.data_ptr()), nchunks, C.c_void_p(self._hyper[1].data_ptr()),
+                  C.c_void_p(self._fresh.data_ptr()), 1 if clear else 0, coef, _stream())
+        torch.autograd.graph.increment_version(ps)      # the kernel wrote p in place: invalidate packed-weight caches
         return loss

@@ -520,6 +520,29 @@ int fva_adam_step(const void* const* ptrs, const int64_t* sizes, int32_t n, int6
 int fva_adam_step_dev(const void* const* ptrs, const int64_t* sizes, int32_t n, int64_t max_size, const float* lr_dev, float beta1,
                       float beta2, float eps, float weight_decay, double* state_dev, float grad_scale, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Optimizer: torch.optim.SGD semantics (demos/faster_rcnn/train.py:91-109: momentum 0.937, Nesterov, parameter groups) with the
+ * demo's global gradient-norm clipping (demos/faster_rcnn/cfg/_fit.py:6-17) on the device; multi-tensor, every group in one launch.
+ * The work is split into chunks of fva_sgd_chunk_elems() elements, one block each:
+ *   tab_dev: int64 [6][n] in device memory = param | grad | momentum buffer (0: none, plain SGD) fp32 pointers | element count |
+ *            parameter-group index (row of hyper_dev) | slot in fresh_dev;
+ *   chunks_dev: int64 [nchunks] = (tensor index << 32) | chunk number within the tensor (built once by the host);
+ *   hyper_dev: float [groups][5] = lr, weight_decay, momentum, 1 - dampening, nesterov (0 or 1), read at run time (a captured HIP
+ *            graph follows later host rewrites of the table: LR schedules);
+ *   fresh_dev: int32 per slot, non-zero while a momentum buffer has no history (the update sets buf = g, torch's clone).
+ * Pointers may be any 4-byte aligned address (16-byte vector path where a tensor's pointers allow it). */
+int fva_sgd_chunk_elems(void);
+/* partial_dev: double [nchunks] scratch; out_dev[0] = fp32 global L2 norm of every grad in the table, out_dev[1] = the reference's
+ * coefficient clip_norm / max(norm, clip_norm) computed in double as Python does, rounded to fp32 (Python max: a NaN norm gives NaN, an infinite one 0).  Fixed summation order (fp64
+ * per chunk, chunk order across chunks): bit-identical from run to run.  No host synchronisation. */
+int fva_sgd_clip_coef(const int64_t* tab_dev, int32_t n, const int64_t* chunks_dev, int32_t nchunks, double* partial_dev,
+                      double clip_norm, float* out_dev, void* stream);
+/* p -= lr * step(coef * grad) in torch's order (weight decay into the gradient, momentum buffer, Nesterov); coef_dev: device
+ * scalar (out_dev + 1 of fva_sgd_clip_coef) or NULL for 1.  The gradients themselves are not rewritten.  clear_fresh != 0: after
+ * the update, zero the fresh flags of the table's slots (their buffers now have history). */
+int fva_sgd_step(const int64_t* tab_dev, int32_t n, const int64_t* chunks_dev, int32_t nchunks, const float* hyper_dev,
+                 int32_t* fresh_dev, int32_t clear_fresh, const float* coef_dev, void* stream);
+
 /* Gradient bucket fill for the data-parallel all-reduce (parallel.GradientReducer; the reference's nn.DataParallel gathers
  * gradients tensor by tensor, demos/yolov3_u/train.py:85): dst[offs[t] + i] = src_t[i], converted to dst_dtype (FVA_F32 or
  * FVA_BF16), for n fp32 source tensors in one launch.  table_dev: 3n int64 in device memory = source pointers | element counts |
