@@ -176,10 +176,17 @@ PROTOTYPES = {
     'fva_roi_align_fwd': (_I, [_I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _F, _I, _P]),
     'fva_roi_align_bwd': (_I, [_P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _F, _I, _P]),
     'fva_nms_select': (_I, [_P, _P, _I, _I, _I, C.POINTER(NmsParams), _P, _L, _P, _P, _P, _P]),
+    'fva_gap_fwd': (_I, [_I, _P, _I, _I, _I, _I, _I, _P, _P]),
+    'fva_gap_bwd': (_I, [_I, _P, _I, _I, _I, _I, _P, _P]),
+    'fva_softmax_ce_workspace': (_L, [_I]),
+    'fva_softmax_ce': (_I, [_P, _P, _I, _P, _I, _I, _I, _P, _P, _P, _P]),
+    'fva_top1_accuracy': (_I, [_P, _I, _P, _I, _I, _I, _P, _P, _P]),
 }
+LABEL_I64, LABEL_F32 = 0, 1
+REDUCE_MEAN, REDUCE_SUM = 0, 1
 UNCHECKED = {'fva_conv_patch_kernel', 'fva_sgd_chunk_elems', 'fva_rows_relu_bwd_rows', 'fva_colour_workspace', 'fva_conv_dgrad_stat_rows', 'fva_bias_relu_bwd_rows', 'fva_colsum_scratch_rows', 'fva_last_error', 'fva_version', 'fva_profile_stop', 'fva_conv_last_kernel', 'fva_conv_packed_elems', 'fva_conv_stat_blocks', 'fva_conv_wgrad_workspace', 'fva_conv_wgrad_plan',
              'fva_stem_stat_blocks', 'fva_stem_fused_blocks', 'fva_stem_wgrad_workspace', 'fva_stem_fwd_workspace', 'fva_stem_wgrad_mfma_workspace', 'fva_bn_bwd_blocks', 'fva_bn_partial_rows', 'fva_yolov3_loss_workspace',
-             'fva_demo_loss_workspace', 'fva_nms_candidates_workspace', 'fva_nms_select_workspace'}
+             'fva_demo_loss_workspace', 'fva_nms_candidates_workspace', 'fva_nms_select_workspace', 'fva_softmax_ce_workspace'}
 
 _lib = None
 

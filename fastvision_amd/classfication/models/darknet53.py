@@ -4,12 +4,12 @@ Same class names, constructor signatures, state_dict keys (``conv0.conv.weight``
 and parameter construction order (so ``torch.manual_seed`` reproduces the reference's init).  The modules only
 *own* parameters; their forward runs the fused HIP path of ``fastvision_amd.ops``:
 conv (MFMA implicit GEMM) -> BatchNorm batch statistics -> SiLU (+ residual add), one autograd node per
-ConvBlock / ResidualBlock.
+ConvBlock / ResidualBlock.  With ``including_top`` the classifier top runs there too: global average pooling
+(``ops.global_avg_pool``) and the fc layer (``fc_ops.linear``) return fp32 logits [B, num_classes].
 """
-import torch
 import torch.nn as nn
 
-from ... import ops
+from ... import fc_ops, ops
 
 __all__ = ['conv3x3', 'conv1x1', 'normalization', 'activation', 'ConvBlock3x3', 'ConvBlock1x1', 'ResidualBlock',
            'Darknet', 'darknet53']
@@ -124,9 +124,8 @@ class Darknet(nn.Module):
             with ops.defer_apply_scope():
                 x = getattr(self, f'res{stage}')(getattr(self, f'conv{stage}')(x))
             taps.append(x)
-        if self.including_top:      # classifier top: outside the accelerated path, plain torch ops on the fp32 copy
-            out = torch.flatten(self.gap(taps[4].float()), 1)
-            return self.fc(out)
+        if self.including_top:      # classifier top: fva_gap_fwd on the halo view of res5, then the biased fc GEMM (fp32 logits)
+            return fc_ops.linear(ops.global_avg_pool(taps[4]), self.fc)
         return [taps[4], taps[3], taps[2]]
 
 

@@ -18,12 +18,70 @@ def one_hot(y, num_classes):
     return torch.zeros((col.size(0), num_classes)).to(y).scatter_(1, col, 1)
 
 
+class _SoftmaxCEFn(torch.autograd.Function):
+    """fva_softmax_ce: value and d loss / d logits in one pass over the rows (+ a one-block finish); backward scales the stored
+    gradient by the upstream scalar on the device (fva_scale_by_device_scalar, an empty launch when it is exactly 1)."""
+
+    @staticmethod
+    def forward(ctx, y_pre, y_true, weights, mean, need_grad):
+        from .. import _lib
+        from ..ops import _p, _stream, require_gpu
+        require_gpu(y_pre, 'CrossEntropyLoss')
+        R, Cc = y_pre.shape
+        for name, t in (('y_true', y_true), ('weights', weights)):
+            # the kernel reads these through raw pointers: a tensor on another device (labels straight from a CPU loader) is refused
+            # here, as torch's own ops refuse mixed devices, instead of being dereferenced on the GPU
+            if t is not None and t.device != y_pre.device:
+                raise RuntimeError(f'CrossEntropyLoss: {name} is on {t.device} but y_pre is on {y_pre.device}: move it to {y_pre.device} first')
+        z = y_pre.detach()
+        z = z if (z.dtype == torch.float32 and z.is_contiguous()) else z.float().contiguous()
+        lab = y_true.detach()
+        if lab.numel() != R:
+            raise RuntimeError(f'CrossEntropyLoss: {lab.numel()} labels for {R} rows')
+        if lab.is_floating_point():
+            lab, code = (lab if lab.dtype == torch.float32 else lab.float()).contiguous(), _lib.LABEL_F32
+        else:
+            lab, code = (lab if lab.dtype == torch.int64 else lab.long()).contiguous(), _lib.LABEL_I64
+        w = None
+        if weights is not None:
+            w = weights.detach()
+            w = (w if w.dtype == torch.float32 else w.float()).contiguous()
+            if w.numel() != R:
+                raise RuntimeError(f'CrossEntropyLoss: {w.numel()} weights for {R} rows')
+        grad = torch.empty_like(z) if need_grad else None          # no [R, C] gradient under torch.no_grad() or for constant logits
+        out = torch.empty(1, dtype=torch.float32, device=z.device)
+        ws = torch.empty(max(_lib.load().fva_softmax_ce_workspace(R), 4), dtype=torch.uint8, device=z.device)
+        _lib.call('fva_softmax_ce', _p(z), _p(lab), code, _p(w), R, Cc, _lib.REDUCE_MEAN if mean else _lib.REDUCE_SUM,
+                  _p(out), _p(grad), _p(ws), _stream())
+        ctx.grads, ctx.dtypes = [grad], [y_pre.dtype]
+        return out.view(())
+
+    @staticmethod
+    def backward(ctx, gout):
+        from ..ops import scale_loss_grads
+        return scale_loss_grads(ctx, gout)[0], None, None, None, None
+
+
 class CrossEntropyLoss(nn.Module):
+    """loss/classification_loss.py:8-33: ``forward(y_pre [N, C], y_true [N] or [N, 1] (integer or integral float), weights [N] or
+    None)``, mean over N (not over the weights) or sum.  Device tensors run fva_softmax_ce (value and gradient in one launch, no host
+    sync); a label outside [0, C) cannot raise there as the reference's ``scatter_`` does -- the loss comes back NaN instead.  Labels
+    and weights must be on y_pre's device (RuntimeError otherwise, as torch raises for mixed devices).  On the device the gradient
+    flows to y_pre only: weights that require grad are refused (RuntimeError) -- the reference would differentiate them -- and under
+    ``torch.no_grad()`` (or for logits that need no gradient) only the value is computed.  CPU tensors run the reference's torch
+    expression, weight gradients included."""
+
     def __init__(self, reduction='mean'):
         super().__init__()
         self.reduction = reduction
 
     def forward(self, y_pre, y_true, weights=None):
+        if y_pre.is_cuda:
+            grad_on = torch.is_grad_enabled()
+            if grad_on and weights is not None and weights.requires_grad:
+                raise RuntimeError('CrossEntropyLoss: on the device the gradient flows to y_pre only; pass weights.detach() '
+                                   '(or compute the weighted loss on CPU tensors)')
+            return _SoftmaxCEFn.apply(y_pre, y_true, weights, self.reduction == 'mean', grad_on and y_pre.requires_grad)
         target = one_hot(y_true, y_pre.size(-1)).float()
         loss = -torch.sum(target * F.log_softmax(y_pre, dim=-1), dim=1)
         if weights is not None:

@@ -1,1 +1,2 @@
-from .map import *   # noqa: F401,F403
+from .map import *        # noqa: F401,F403
+from .accuracy import *   # noqa: F401,F403

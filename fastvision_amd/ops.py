@@ -1027,6 +1027,34 @@ class HeadFn(torch.autograd.Function):
         return dx, dwp[:N].contiguous(), dbias, None
 
 
+class GlobalAvgPoolFn(torch.autograd.Function):
+    """nn.AdaptiveAvgPool2d((1, 1)) + flatten of the classifier top (darknet53.py:65-137): fp32 [B, C] from a halo (or dense) NHWC
+    view, zero-copy (fva_gap_fwd); backward writes the dense NHWC gradient g / (H*W) in the compute dtype (fva_gap_bwd), the buffer
+    the producer's backward takes zero-copy through to_dense."""
+
+    @staticmethod
+    def forward(ctx, x, dtype):
+        require_gpu(x, 'global_avg_pool')
+        flush_pending_apply()
+        _note_consumer(x)             # its gradient comes from fva_gap_bwd, not from a dgrad epilogue
+        keep, x_ptr, x_pad = to_halo(x, dtype, 0)
+        B, Cc, H, W = x.shape
+        out = torch.empty((B, Cc), dtype=torch.float32, device=x.device)
+        _lib.call('fva_gap_fwd', _code(dtype), C.c_void_p(x_ptr), x_pad, B, H, W, Cc, _p(out), _stream())
+        ctx.meta = (B, Cc, H, W, dtype, x.dtype)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        B, Cc, H, W, dtype, xdt = ctx.meta
+        if g.dtype != torch.float32 or not g.is_contiguous():
+            g = g.float().contiguous()
+        dx = torch.empty((B, H, W, Cc), dtype=dtype, device=g.device)
+        _lib.call('fva_gap_bwd', _code(dtype), _p(g), B, H, W, Cc, _p(dx), _stream())
+        gx = dense_view(dx)
+        return (gx if gx.dtype == xdt else gx.to(xdt)), None
+
+
 # ------------------------------------------------------------------------------------------------ thin functional API
 # autograd.Function.forward always runs with grad mode off, and ctx.needs_input_grad ignores torch.no_grad(): the wrappers
 # below note the caller's grad mode here so that inference (no_grad) takes the context-free fused path
@@ -1054,6 +1082,11 @@ def residual(x, cb1, cb2, dtype=None):
 
 def upsample2_concat(up, skip, up_first, dtype=None):
     return UpsampleConcatFn.apply(up, skip, up_first, dtype or get_compute_dtype())
+
+
+def global_avg_pool(x, dtype=None):
+    """Mean over H, W of a feature map [B, C, H, W] -> fp32 [B, C] (the classifier top's AdaptiveAvgPool2d((1, 1)) + flatten)."""
+    return GlobalAvgPoolFn.apply(x, dtype or get_compute_dtype())
 
 
 def head_conv(x, conv, dtype=None):

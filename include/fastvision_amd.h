@@ -610,6 +610,30 @@ int fva_roi_align_fwd(int dtype, const void* feat, int feat_pad, const float* ro
 int fva_roi_align_bwd(const float* grad_out, const float* rois, int K, float* dfeat, int B, int H, int W, int C, int PH, int PW,
                       float spatial_scale, int sampling_ratio, void* stream);
 
+/* ---- Classification top of Darknet-53 (classfication/models/darknet53.py:65-137 with including_top; loss/classification_loss.py:8-33;
+ * metrics/accuracy.py) ----------------------------------------------------------------------------------------------------------
+ * fva_gap_fwd: nn.AdaptiveAvgPool2d((1, 1)) + flatten.  x: NHWC [B][H+2*x_pad][W+2*x_pad][C] of dtype (x_pad 1: a halo buffer, 0:
+ * dense); out fp32 [B][C] = the mean over the H*W pixels, summed in fp32 in a fixed order (no atomics: run-to-run bit-identical).
+ * fva_gap_bwd: dx (dtype, dense NHWC [B][H][W][C]) = g[b][c] / (H*W), g fp32 [B][C].
+ * fva_softmax_ce: CrossEntropyLoss, -sum(onehot(label) * log_softmax(z), 1) * w, over logits fp32 [R][C]; labels [R] int64
+ * (FVA_LABEL_I64) or fp32 holding integer values (FVA_LABEL_F32); weights fp32 [R] or NULL (= 1).  loss_out[0] = the row losses
+ * summed in double in a fixed order, divided by R for FVA_REDUCE_MEAN (not by the sum of the weights) or not for FVA_REDUCE_SUM;
+ * grad (optional, [R][C]) = w_r * (softmax(z_r) - onehot) (times 1/R for the mean).  workspace: fva_softmax_ce_workspace(R) bytes.
+ * A label that is < 0, >= C or (fp32) not an integer cannot raise on the device: that row's loss and gradient are NaN, so loss_out
+ * is NaN, and no memory is indexed with it; the other rows' gradients are unaffected.
+ * fva_top1_accuracy: out[0] = (number of rows whose argmax equals the label) / R, fp32.  logits [R][C] of logits_dtype (FVA_F32 /
+ * FVA_BF16); argmax as torch.argmax (first index among equal maxima; a NaN is the maximum, the first NaN wins); an out-of-range
+ * label simply never matches.  workspace: R int32.  Deterministic. */
+typedef enum { FVA_LABEL_I64 = 0, FVA_LABEL_F32 = 1 } fva_label_dtype;
+typedef enum { FVA_REDUCE_MEAN = 0, FVA_REDUCE_SUM = 1 } fva_reduction;
+int fva_gap_fwd(int dtype, const void* x, int x_pad, int B, int H, int W, int C, float* out, void* stream);
+int fva_gap_bwd(int dtype, const float* g, int B, int H, int W, int C, void* dx, void* stream);
+int64_t fva_softmax_ce_workspace(int32_t R);
+int fva_softmax_ce(const float* logits, const void* labels, int label_dtype, const float* weights, int32_t R, int32_t C, int32_t reduction,
+                   float* loss_out, float* grad, void* workspace, void* stream);
+int fva_top1_accuracy(const void* logits, int logits_dtype, const void* labels, int label_dtype, int32_t R, int32_t C, float* out,
+                      void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
