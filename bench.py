@@ -10,11 +10,16 @@ torch.distributed.run directly (RANK / WORLD_SIZE set) it is simply one of the r
 
 A step = forward + target assignment + yolov3_loss + backward + gradient all-reduce (N > 1) + Adam on one synthetic
 batch that is resident in HBM before the timed region.  Rank 0 prints ONE JSON line: BASELINE.json's metric
-(images/sec, whole job), plus
-  roofline     -- the dominant kernel class (MFMA implicit-GEMM convolution), algorithmic FLOPs per launch divided by
-                  its average launch duration, measured live with HIP events on the launch stream in the timed region;
-  cpu_baseline -- the CPU oracle (a port of the reference's CPU path: same model / loss / Adam / step contract of
-                  utils/fit.py:52-66) timed on this host's cores on a bounded sample (N = 1 only).
+(images/sec, whole job).  A plain run does only what that figure needs: set up, warm up, choose how the step is issued,
+time the steps, write --dump-outputs, print the line.  With --full the line also carries what takes runs of its own:
+  roofline       -- the dominant kernel class (MFMA implicit-GEMM convolution), algorithmic FLOPs per launch divided by
+                    its average launch duration, measured live with HIP events on the launch stream in the timed region
+                    (eager steps carry these spans in a plain run too, so their roofline is in every line; a replayed
+                    graph's needs a capture of its own);
+  kernels, conv3x3 -- exclusive per-class convolution figures from an untimed probe, and the shader clock under load;
+  cpu_baseline   -- the CPU oracle (a port of the reference's CPU path: same model / loss / Adam / step contract of
+                    utils/fit.py:52-66) timed on this host's cores on a bounded sample (N = 1 only);
+  secondary_fp32, secondary -- BASELINE configs 2 (fp32, with its parity line against the oracle) and 5 (Faster R-CNN).
 """
 import argparse
 import json
@@ -290,7 +295,10 @@ def main():
     ap.add_argument('--wire', default='fp32', choices=['fp32', 'bf16'],
                     help='dtype of the gradient buckets on the wire for --gpus N > 1: fp32 is what the reference\'s DataParallel reduces (default); '
                          'bf16 halves the bytes over xGMI (recorded in config.grad_wire_dtype)')
-    ap.add_argument('--no-secondary', action='store_true', help='skip the Faster R-CNN (BASELINE config 5) block of the default one-GPU line')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what the headline figure does not need: per-class kernel figures, the roofline of a replayed graph, '
+                         'the CPU baselines and the BASELINE config 2 / 5 blocks of the default one-GPU line')
+    ap.add_argument('--no-secondary', action='store_true', help='with --full: skip the BASELINE config 2 / 5 blocks of the default one-GPU line')
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
                     help='write what the last timed step computed (loss, sampled parameters and gradients, BatchNorm buffers) as DIR/<name>.npy; '
                          'the training state is reset to the state after the warm-up steps before the timed region, so equal arguments give '
@@ -307,7 +315,7 @@ def main():
     if args.model == 'faster_rcnn':
         sys.path.insert(0, os.path.join(ROOT, 'tools'))
         import bench_faster
-        bench_faster.main(steps=args.steps, warmup=args.warmup, cpu_baseline=not args.no_cpu_baseline)
+        bench_faster.main(steps=args.steps, warmup=args.warmup, cpu_baseline=args.full and not args.no_cpu_baseline, probe=args.full)
         return
 
     import torch.distributed as dist
@@ -393,39 +401,40 @@ def main():
     # autotuning, settle windows); the state after the warm-up is put back right before the timed region
     from fastvision_amd.graphs import restore_train_state, snapshot_train_state
     dump_snap = snapshot_train_state(net, opt) if args.dump_outputs is not None else None
-    # untimed probe for the informative `kernels` table: all three convolution classes bracketed with HIP events inside the
-    # library, issued eagerly with the weight gradients on the launch stream like everything else, so that every launch has the
-    # GPU to itself (exclusive durations).  In the product configuration the wgrad launches run on the library's low-priority
-    # side stream, concurrently with the rest of the backward pass: event-to-event durations of wgrad and dgrad launches then
-    # include time spent sharing the GPU.
     from fastvision_amd import ops as fva_ops
-    probe_steps = 3
-    side_was = fva_ops.set_wgrad_side_stream(False)
-    step()
-    with KernelTimer(pool=calls_per_step * probe_steps + 8) as probe:
-        for _ in range(probe_steps):
-            step()
-        fence()
-    # the shader clock under load: MI355X runs its matrix pipes well below the 2.4 GHz the 2.5 PFLOP/s peak is quoted at.
-    # One more untimed step with the 8-phase kernel's diagnostic stamps on: cycle counter / wall clock over each block's
-    # k-loop (bf16 only -- the 8-phase kernel is a bf16 kernel).
-    clock_mhz = None
-    import ctypes as C
     from fastvision_amd import _lib as fva_lib
-    if args.dtype == 'bf16':
-        nstamp = 8192
-        stamps = torch.zeros(8 * nstamp, dtype=torch.int64, device=dev)
-        fva_lib.call('fva_conv_debug_stamps', C.c_void_p(stamps.data_ptr()), nstamp)
+    side_was = fva_ops._SIDE['on']
+    probe_steps, probe_summ, clock_mhz = 3, None, None
+    if args.full:
+        # untimed probe for the informative `kernels` table: all three convolution classes bracketed with HIP events inside the
+        # library, issued eagerly with the weight gradients on the launch stream like everything else, so that every launch has the
+        # GPU to itself (exclusive durations).  In the product configuration the wgrad launches run on the library's low-priority
+        # side stream, concurrently with the rest of the backward pass: event-to-event durations of wgrad and dgrad launches then
+        # include time spent sharing the GPU.
+        fva_ops.set_wgrad_side_stream(False)
         step()
-        fence()
-        fva_lib.call('fva_conv_debug_stamps', C.c_void_p(0), 0)
-        st = stamps.view(-1, 8).cpu()
-        st = st[st[:, 3] > 0]
-        if len(st):
-            wall_us = (st[:, 2] - st[:, 1]).double() / 100.0
-            clock_mhz = float(((st[:, 6] - st[:, 5]).double() / wall_us).median())
-    fva_ops.set_wgrad_side_stream(side_was)
-    probe_summ = probe.summary()
+        with KernelTimer(pool=calls_per_step * probe_steps + 8) as probe:
+            for _ in range(probe_steps):
+                step()
+            fence()
+        # the shader clock under load: MI355X runs its matrix pipes well below the 2.4 GHz the 2.5 PFLOP/s peak is quoted at.
+        # One more untimed step with the 8-phase kernel's diagnostic stamps on: cycle counter / wall clock over each block's
+        # k-loop (bf16 only -- the 8-phase kernel is a bf16 kernel).
+        import ctypes as C
+        if args.dtype == 'bf16':
+            nstamp = 8192
+            stamps = torch.zeros(8 * nstamp, dtype=torch.int64, device=dev)
+            fva_lib.call('fva_conv_debug_stamps', C.c_void_p(stamps.data_ptr()), nstamp)
+            step()
+            fence()
+            fva_lib.call('fva_conv_debug_stamps', C.c_void_p(0), 0)
+            st = stamps.view(-1, 8).cpu()
+            st = st[st[:, 3] > 0]
+            if len(st):
+                wall_us = (st[:, 2] - st[:, 1]).double() / 100.0
+                clock_mhz = float(((st[:, 6] - st[:, 5]).double() / wall_us).median())
+        fva_ops.set_wgrad_side_stream(side_was)
+        probe_summ = probe.summary()
     dom = 'conv_fwd'
 
     # The side stream is the product default, but whether two HIP streams (or two branches of a graph) share the GPU to advantage
@@ -585,7 +594,9 @@ def main():
     final_loss = float(loss.detach())
     dumped = dump_outputs(args.dump_outputs, net, final_loss) if args.dump_outputs is not None and rank == 0 else None
     roof_how = 'every launch' if args.shapes else f'every {SAMPLE_STRIDE}th launch of the class over the timed region'
-    if use_graph:
+    if use_graph and not args.full:
+        summ = None                 # the replays carry no spans: the roofline of the graph step needs runs of its own (--full)
+    elif use_graph:
         # the same step captured with event-record nodes around every forward convolution launch, replayed right after the
         # timed region; falls back to eagerly issued steps if this runtime does not time events recorded by graph nodes
         summ = None
@@ -633,23 +644,6 @@ def main():
         ms_step = elapsed / args.steps * 1e3
         ips = args.batch * world * args.steps / elapsed
         peak = PEAK_BF16_TFLOPS if args.dtype == 'bf16' else PEAK_F32_TFLOPS
-        d = summ[dom]
-        kernel_name = {'conv_fwd': 'igemm8_kernel / igemm_kernel <EPI_STATS>: implicit-GEMM convolution, forward launches (fva_conv_fwd[_acc]; the 13 1x1 launches that also carry the apply pass of the block before them are a class of their own: kernels.conv_fwd_fused)',
-                       'conv_dgrad': 'igemm_kernel<EPI_PLAIN> (fva_conv_dgrad)',
-                       'conv_wgrad': 'wgrad_kernel (+reduce) (fva_conv_wgrad)'}[dom]
-        traffic = None
-        tpath = os.path.join(ROOT, 'profiles', 'traffic.json')
-        if os.path.exists(tpath):
-            traffic = (json.load(open(tpath)).get(dom) or {}).get('bytes_per_launch')   # measured offline with PMC counters
-        # north_star's own yardstick: MFMA utilisation on the 3x3 convolutions (exclusive probe figures, all three classes)
-        p3 = probe.summary(ksize=3)
-        f3, t3 = sum(v['flop_total'] for v in p3.values()), sum(v['ms_total'] for v in p3.values())
-        tf3 = f3 / (t3 * 1e-3) / 1e12 if t3 > 0 else 0.0
-        conv3x3 = {'tflops': round(tf3, 2), 'frac_of_peak': round(tf3 / peak, 4), 'ms_per_step': round(t3 / probe_steps, 3),
-                   'frac_at_measured_clock': None if clock_mhz is None else round(tf3 / (peak * clock_mhz / 2400.0), 4),
-                   'per_class_tflops': {k: round(v['tflops'], 2) for k, v in p3.items()},
-                   'note': 'all 3x3 convolution launches of the step (forward, dgrad, wgrad incl. its reduce; thin and stride-2 '
-                           'layers included), exclusive timings of the probe pass'}
         out = {
             'metric': METRIC, 'value': round(ips, 2), 'unit': 'images/sec', 'n_gpus': world, 'steps': args.steps,
             'warmup': args.warmup, 'ms_per_step': round(ms_step, 3), 'higher_is_better': True, 'scaling': 'weak',
@@ -662,30 +656,52 @@ def main():
                        'bn_backward_statistics_in_dgrad': bool(fva_ops._BN_FUSE[0]),
                        'host_env': {k: os.environ.get(k) for k in ('HSA_ENABLE_INTERRUPT', 'GPU_MAX_HW_QUEUES', 'FVA_WGRAD_STREAM', 'FVA_WGRAD_PLAN', 'FVA_BN_ACC', 'FVA_FUSE_APPLY', 'FVA_BN_FUSE')
                                     if os.environ.get(k) is not None}},
-            'roofline': {'bound': 'mfma', 'kernel': kernel_name, 'achieved': round(d['tflops'], 2), 'peak': peak, 'unit': 'TFLOP/s',
-                         'frac': round(d['tflops'] / peak, 4), 'traffic': traffic,
-                         'launches_per_step': probe_summ[dom]['launches'] // probe_steps, 'launches_timed': d['launches'],
-                         'sampling': roof_how,
-                         # rounds 1-3 pooled ALL forward launches; the 13 launches that now also carry an apply pass left that class in
-                         # round 4 -- the same pooled figure, from the probe pass, for comparison across rounds
-                         'pooled_with_fused_launches': (lambda a, b: None if b is None else {
-                             'achieved': round((a['flop_total'] + b['flop_total']) / ((a['ms_total'] + b['ms_total']) * 1e-3) / 1e12, 2),
-                             'frac': round((a['flop_total'] + b['flop_total']) / ((a['ms_total'] + b['ms_total']) * 1e-3) / 1e12 / peak, 4),
-                             'launches_per_step': (a['launches'] + b['launches']) // probe_steps,
-                             'note': 'probe pass (exclusive), plain + fused forward launches'})(probe_summ[dom], probe_summ.get('conv_fwd_fused')) if dom == 'conv_fwd' else None,
-                         'avg_launch_ms': round(d['ms_avg'], 4), 'gflop_per_launch': round(d['flop_per_launch'] / 1e9, 3),
-                         'ms_per_step': round(probe_summ[dom]['ms_total'] / probe_steps, 3),
-                         'shader_clock_mhz_under_load': None if clock_mhz is None else round(clock_mhz),
-                         'peak_at_that_clock': None if clock_mhz is None else round(peak * clock_mhz / 2400.0, 1),
-                         'frac_at_that_clock': None if clock_mhz is None else round(d['tflops'] / (peak * clock_mhz / 2400.0), 4),
-                         'clock_note': 'peak is the nominal dense figure at 2400 MHz; the clock is the median, over the blocks of the 8-phase '
-                                       'convolution launches of one untimed step, of cycle counter / wall clock across the k-loop'},
-            'kernels': {k: {'tflops': round(v['tflops'], 2), 'ms_per_step': round(v['ms_total'] / probe_steps, 3),
-                            'launches_per_step': v['launches'] // probe_steps} for k, v in probe_summ.items()},
-            'conv3x3': conv3x3,
-            'kernels_note': f'exclusive per-class figures: all classes bracketed on {probe_steps} untimed steps just before the '
-                            'timed region, with the weight gradients on the launch stream (in the timed region they run on a '
-                            'low-priority side stream beside the rest of backward, and only the roofline class is bracketed)',
+        }
+        if summ is not None:
+            d = summ[dom]
+            kernel_name = {'conv_fwd': 'igemm8_kernel / igemm_kernel <EPI_STATS>: implicit-GEMM convolution, forward launches (fva_conv_fwd[_acc]; the 13 1x1 launches that also carry the apply pass of the block before them are a class of their own: kernels.conv_fwd_fused)',
+                           'conv_dgrad': 'igemm_kernel<EPI_PLAIN> (fva_conv_dgrad)',
+                           'conv_wgrad': 'wgrad_kernel (+reduce) (fva_conv_wgrad)'}[dom]
+            traffic = None
+            tpath = os.path.join(ROOT, 'profiles', 'traffic.json')
+            if os.path.exists(tpath):
+                traffic = (json.load(open(tpath)).get(dom) or {}).get('bytes_per_launch')   # measured offline with PMC counters
+            roofline = {'bound': 'mfma', 'kernel': kernel_name, 'achieved': round(d['tflops'], 2), 'peak': peak, 'unit': 'TFLOP/s',
+                        'frac': round(d['tflops'] / peak, 4), 'traffic': traffic, 'launches_timed': d['launches'], 'sampling': roof_how,
+                        'avg_launch_ms': round(d['ms_avg'], 4), 'gflop_per_launch': round(d['flop_per_launch'] / 1e9, 3)}
+            if probe_summ is not None:
+                roofline.update({
+                    'launches_per_step': probe_summ[dom]['launches'] // probe_steps,
+                    # rounds 1-3 pooled ALL forward launches; the 13 launches that now also carry an apply pass left that class in
+                    # round 4 -- the same pooled figure, from the probe pass, for comparison across rounds
+                    'pooled_with_fused_launches': (lambda a, b: None if b is None else {
+                        'achieved': round((a['flop_total'] + b['flop_total']) / ((a['ms_total'] + b['ms_total']) * 1e-3) / 1e12, 2),
+                        'frac': round((a['flop_total'] + b['flop_total']) / ((a['ms_total'] + b['ms_total']) * 1e-3) / 1e12 / peak, 4),
+                        'launches_per_step': (a['launches'] + b['launches']) // probe_steps,
+                        'note': 'probe pass (exclusive), plain + fused forward launches'})(probe_summ[dom], probe_summ.get('conv_fwd_fused')) if dom == 'conv_fwd' else None,
+                    'ms_per_step': round(probe_summ[dom]['ms_total'] / probe_steps, 3),
+                    'shader_clock_mhz_under_load': None if clock_mhz is None else round(clock_mhz),
+                    'peak_at_that_clock': None if clock_mhz is None else round(peak * clock_mhz / 2400.0, 1),
+                    'frac_at_that_clock': None if clock_mhz is None else round(d['tflops'] / (peak * clock_mhz / 2400.0), 4),
+                    'clock_note': 'peak is the nominal dense figure at 2400 MHz; the clock is the median, over the blocks of the 8-phase '
+                                  'convolution launches of one untimed step, of cycle counter / wall clock across the k-loop'})
+            out['roofline'] = roofline
+        if probe_summ is not None:
+            # north_star's own yardstick: MFMA utilisation on the 3x3 convolutions (exclusive probe figures, all three classes)
+            p3 = probe.summary(ksize=3)
+            f3, t3 = sum(v['flop_total'] for v in p3.values()), sum(v['ms_total'] for v in p3.values())
+            tf3 = f3 / (t3 * 1e-3) / 1e12 if t3 > 0 else 0.0
+            out['kernels'] = {k: {'tflops': round(v['tflops'], 2), 'ms_per_step': round(v['ms_total'] / probe_steps, 3),
+                                  'launches_per_step': v['launches'] // probe_steps} for k, v in probe_summ.items()}
+            out['conv3x3'] = {'tflops': round(tf3, 2), 'frac_of_peak': round(tf3 / peak, 4), 'ms_per_step': round(t3 / probe_steps, 3),
+                              'frac_at_measured_clock': None if clock_mhz is None else round(tf3 / (peak * clock_mhz / 2400.0), 4),
+                              'per_class_tflops': {k: round(v['tflops'], 2) for k, v in p3.items()},
+                              'note': 'all 3x3 convolution launches of the step (forward, dgrad, wgrad incl. its reduce; thin and stride-2 '
+                                      'layers included), exclusive timings of the probe pass'}
+            out['kernels_note'] = (f'exclusive per-class figures: all classes bracketed on {probe_steps} untimed steps just before the '
+                                   'timed region, with the weight gradients on the launch stream (in the timed region they run on a '
+                                   'low-priority side stream beside the rest of backward, and only the roofline class is bracketed)')
+        out.update({
             'wgrad_side_stream': bool(side_use), 'side_stream_check_ms_per_step': side_check,
             'hip_graph': graph_info if graph_info is not None else False,
             'step_tflops': round(TRAIN_GFLOP_PER_IMAGE_640 * (args.size / 640.0) ** 2 * args.batch / 1e3 / (ms_step * 1e-3), 2),
@@ -701,7 +717,7 @@ def main():
                           'alloc_retries': int(ms1.get('num_alloc_retries', 0)),
                           'reserved_gb': round(ms1.get('reserved_bytes.all.current', 0) / 2 ** 30, 2),
                           'active_peak_gb': round(ms1.get('active_bytes.all.peak', 0) / 2 ** 30, 2)},
-        }
+        })
         if dumped is not None:
             out['dump_outputs'] = dumped
         if args.shapes:
@@ -712,9 +728,9 @@ def main():
             out['dp'] = reducer.stats()
             out['dp']['parameters_identical_across_ranks'] = params_identical
             out['config']['grad_wire_dtype'] = out['dp']['wire_dtype']
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out['cpu_baseline'] = cpu_baseline(args.size, args.batch)
-        default_line = world == 1 and not args.no_secondary and not args.shapes and args.surface == 'lib' and args.dtype == 'bf16' and args.batch == 32 and args.size == 640
+        default_line = args.full and world == 1 and not args.no_secondary and not args.shapes and args.surface == 'lib' and args.dtype == 'bf16' and args.batch == 32 and args.size == 640
         if default_line:
             # BASELINE config 2 at the reference's own precision (fp32 end to end) in the same driver-run line
             try:

@@ -4,7 +4,7 @@ out=$1; shift; mkdir -p "$out"
 for rep in 1 2; do
   for spec in "$@"; do
     label=${spec%%=*}; envs=${spec#*=}
-    env $envs python bench.py --steps 20 --no-cpu-baseline --no-graph --no-secondary 2>"$out/$label.$rep.err" > "$out/$label.$rep.json"
+    env $envs python bench.py --full --steps 20 --no-cpu-baseline --no-graph --no-secondary 2>"$out/$label.$rep.err" > "$out/$label.$rep.json"
     python - "$out/$label.$rep.json" "$label" <<'PY' | tee -a "$out/summary.txt"
 import json, sys
 d = json.load(open(sys.argv[1]))

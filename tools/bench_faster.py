@@ -19,7 +19,8 @@ from fastvision_amd.demos.faster_rcnn.models import Faster_Rcnn
 DEV = 'cuda:0'
 
 
-def main(steps=None, warmup=3, cpu_baseline=True, emit=True):
+def main(steps=None, warmup=3, cpu_baseline=True, emit=True, probe=True):
+    """probe: also time 3 more steps with every convolution bracketed by HIP events (`roofline`, `kernels`)."""
     if steps is None:
         steps = int(sys.argv[1]) if len(sys.argv) > 1 else 10
     B, H, W, NC = 4, 800, 1333, 20
@@ -53,27 +54,30 @@ def main(steps=None, warmup=3, cpu_baseline=True, emit=True):
             loss = step()
         torch.cuda.synchronize()
         ms = (time.perf_counter() - t0) / steps * 1e3
-    # exclusive per-class convolution figures (HIP events inside the library, weight gradients on the launch stream for this probe)
-    from fastvision_amd import ops as fva_ops
-    from fastvision_amd.profiler import KernelTimer
-    was = fva_ops.set_wgrad_side_stream(False)
-    with fastvision_amd.compute_dtype(torch.bfloat16):
-        step()
-        torch.cuda.synchronize()
-        with KernelTimer(pool=4096) as kt:
-            for _ in range(3):
-                step()
+    figures = {}
+    if probe:
+        # exclusive per-class convolution figures (HIP events inside the library, weight gradients on the launch stream for this probe)
+        from fastvision_amd import ops as fva_ops
+        from fastvision_amd.profiler import KernelTimer
+        was = fva_ops.set_wgrad_side_stream(False)
+        with fastvision_amd.compute_dtype(torch.bfloat16):
+            step()
             torch.cuda.synchronize()
-    fva_ops.set_wgrad_side_stream(was)
-    summ = kt.summary()
-    dom = max(summ, key=lambda k: summ[k]['ms_total'])
-    peak = 2500.0
-    roofline = {'bound': 'mfma', 'kernel': {'conv_fwd': 'implicit-GEMM convolution forward (igemm8_kernel / igemm_kernel, bias + ReLU epilogue)',
-                                              'conv_dgrad': 'implicit-GEMM convolution dgrad', 'conv_wgrad': 'weight gradient (wgrad8_kernel / wgrad_kernel + reduce)'}[dom],
-                'achieved': round(summ[dom]['tflops'], 2), 'peak': peak, 'unit': 'TFLOP/s', 'frac': round(summ[dom]['tflops'] / peak, 4), 'traffic': None,
-                'avg_launch_ms': round(summ[dom]['ms_avg'], 4), 'launches_per_step': summ[dom]['launches'] // 3,
-                'note': 'dominant convolution class by summed launch time; exclusive timings of a 3-step probe with every kernel on one stream'}
-    kernels = {k: {'tflops': round(v['tflops'], 2), 'ms_per_step': round(v['ms_total'] / 3, 3), 'launches_per_step': v['launches'] // 3} for k, v in summ.items()}
+            with KernelTimer(pool=4096) as kt:
+                for _ in range(3):
+                    step()
+                torch.cuda.synchronize()
+        fva_ops.set_wgrad_side_stream(was)
+        summ = kt.summary()
+        dom = max(summ, key=lambda k: summ[k]['ms_total'])
+        peak = 2500.0
+        figures['roofline'] = {'bound': 'mfma', 'kernel': {'conv_fwd': 'implicit-GEMM convolution forward (igemm8_kernel / igemm_kernel, bias + ReLU epilogue)',
+                                                           'conv_dgrad': 'implicit-GEMM convolution dgrad', 'conv_wgrad': 'weight gradient (wgrad8_kernel / wgrad_kernel + reduce)'}[dom],
+                               'achieved': round(summ[dom]['tflops'], 2), 'peak': peak, 'unit': 'TFLOP/s', 'frac': round(summ[dom]['tflops'] / peak, 4), 'traffic': None,
+                               'avg_launch_ms': round(summ[dom]['ms_avg'], 4), 'launches_per_step': summ[dom]['launches'] // 3,
+                               'note': 'dominant convolution class by summed launch time; exclusive timings of a 3-step probe with every kernel on one stream'}
+        figures['kernels'] = {k: {'tflops': round(v['tflops'], 2), 'ms_per_step': round(v['ms_total'] / 3, 3), 'launches_per_step': v['launches'] // 3}
+                              for k, v in summ.items()}
     cpu = None
     if cpu_baseline:
         # CPU baseline: the oracle (oracle/faster.py: plain torch fp32 ops over the same parameters) on a bounded sample -- one image of
@@ -107,7 +111,7 @@ def main(steps=None, warmup=3, cpu_baseline=True, emit=True):
            'config': {'workload': f'Faster R-CNN (the reference demo: VGG16 stride-16 backbone + RPN + Fast head) train step {B}x3x{H}x{W} bf16, '
                                   f'{NC} classes, 128+128 RPN / 16+48 Fast samples per image, grad-norm clip + Nesterov SGD (BASELINE config 5)',
                       'global_batch': B, 'parallelism': 'dp1'},
-           'roofline': roofline, 'kernels': kernels, 'loss': round(float(loss.detach()), 4),
+           **figures, 'loss': round(float(loss.detach()), 4),
            'note': 'conv / pool / RoIAlign / matchers / proposal layer / fully connected layers / losses on the HIP kernels; host-inclusive '
                    '(each step reads sample counts back like the reference)'}
     if cpu is not None:

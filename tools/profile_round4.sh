@@ -4,7 +4,7 @@
 set -o pipefail
 out=$1; mkdir -p "$out"
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
-timeout -k 10 500 python3 bench.py > "$out/bench.json" 2> "$out/bench.err" || exit 1
+timeout -k 10 500 python3 bench.py --full > "$out/bench.json" 2> "$out/bench.err" || exit 1
 B="python3 bench.py --no-cpu-baseline --no-secondary --steps 20 --no-graph"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$out/kt" -o kt -- $B > "$out/kt.json" 2> "$out/kt.log" || exit 1
 db=$(ls "$out"/kt/*.db "$out"/kt/*/*.db 2>/dev/null | head -1)
