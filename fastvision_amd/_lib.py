@@ -181,6 +181,15 @@ PROTOTYPES = {
     'fva_softmax_ce_workspace': (_L, [_I]),
     'fva_softmax_ce': (_I, [_P, _P, _I, _P, _I, _I, _I, _P, _P, _P, _P]),
     'fva_top1_accuracy': (_I, [_P, _I, _P, _I, _I, _I, _P, _P, _P]),
+    'fva_bn_relu_apply': (_I, [_I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    'fva_bn_relu_bwd_reduce': (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _I, _L, _I, _P]),
+    'fva_bn_relu_bwd_apply': (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    'fva_bn_bias_running_mean': (_I, [_I, _P, _P, _F, _P]),
+    'fva_bn_eval_coeffs_bias': (_I, [_I, _P, _P, _P, _P, _P, _F, _P, _P, _P]),
+    'fva_adaptive_avgpool7_fwd': (_I, [_I, _P, _I, _I, _I, _I, _I, _P, _P]),
+    'fva_adaptive_avgpool7_bwd': (_I, [_I, _P, _I, _I, _I, _I, _P, _P]),
+    'fva_dropout_fwd': (_I, [_I, _P, _P, _L, _F, _P, _P]),
+    'fva_dropout_bwd': (_I, [_I, _P, _P, _P, _L, _F, _P]),
 }
 LABEL_I64, LABEL_F32 = 0, 1
 REDUCE_MEAN, REDUCE_SUM = 0, 1

@@ -7,6 +7,8 @@
 //
 // Replaces nn.BatchNorm2d / nn.SiLU / `identity + conv2` (reference classfication/models/darknet53.py:11-17,
 // 28-31, 58-62) and nn.Upsample + torch.cat (detection/neck/yolov3neck.py:71,105,110).
+#include <type_traits>
+
 #include "common.h"
 
 namespace {
@@ -923,6 +925,277 @@ int fva_cast_nhwc(const void* src, int src_dtype, int src_pad, void* dst, int ds
     else
         hipLaunchKernelGGL((cast_nhwc_kernel<float, float>), g, b, 0, s, (const float*)src, src_pad, (float*)dst, dst_pad, B, H, W, C);
     FVA_LAUNCH_CHECK("cast_nhwc_kernel");
+    return FVA_OK;
+}
+
+}  // extern "C"
+
+// =========================================================================================================
+// BatchNorm2d + ReLU (reference classfication/models/vgg.py:39-48, `Conv2d(bias=True) -> BatchNorm2d -> ReLU`): the three streaming
+// passes of the SiLU path with the activation exchanged, as kernels of their own (the SiLU kernels above are untouched: same bits).
+// Table form only (fva_conv_fwd's statistics table + fva_bn_finalize / fva_bn_bwd_finalize).  Same shapes of access: one block per padded
+// row, a lane keeps its 16-byte channel chunk for the whole row, FVA_BN_UNROLL chunks in flight, inputs read non-temporal, the zero
+// border written by the pass itself, no atomics.  Bytes per element (bf16): apply 2 + 2; backward pass 1: 4; pass 2: 4 + 2.
+// u = y * scale + shift is recomputed from y in the backward passes (the stored z is rounded: z == 0 and u > 0 can disagree).
+namespace {
+
+__device__ __forceinline__ float relu_keep_nan(float u) { return u <= 0.f ? 0.f : u; }       // a NaN stays a NaN, as in torch.relu
+
+template <typename T>
+__global__ __launch_bounds__(256) void bn_relu_apply_kernel(const T* __restrict__ y, const float* __restrict__ scale,
+                                                            const float* __restrict__ shift, T* __restrict__ z, const HaloIdx h) {
+    constexpr int EPC = Vec16<T>::N, U = FVA_BN_UNROLL;
+    const int row_chunks = h.Wp * h.cpp;
+    const int cmask = h.cpp - 1, cshift = 31 - __builtin_clz(h.cpp);
+    const int cc = threadIdx.x & cmask;
+    const int row = blockIdx.x, b = row / h.Hp, yy = row - b * h.Hp - h.pad;
+    T* zrow = z + (int64_t)row * row_chunks * EPC;
+    if (yy < 0 || yy >= h.H) {          // a border row: zeros (block-uniform branch)
+        Vec16<T> zero;
+#pragma unroll
+        for (int e = 0; e < EPC; ++e) zero.set(e, 0.f);
+        for (int i = threadIdx.x; i < row_chunks; i += 256) *(Vec16<T>*)(zrow + (int64_t)i * EPC) = zero;
+        return;
+    }
+    const T* yrow = y + ((int64_t)b * h.H + yy) * h.W * h.C;
+    float sc[EPC], sh[EPC];
+#pragma unroll
+    for (int e = 0; e < EPC; ++e) {
+        sc[e] = scale[cc * EPC + e];
+        sh[e] = shift[cc * EPC + e];
+    }
+    for (int i0 = threadIdx.x; i0 < row_chunks; i0 += 256 * U) {
+        Vec16<T> v[U];
+        bool ok[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {       // masked chunks read a clamped address (pixel 0 of the row) and store zeros
+            const int i = i0 + u * 256;
+            const int xx = (i >> cshift) - h.pad;
+            ok[u] = i < row_chunks && xx >= 0 && xx < h.W;
+            v[u] = ld_last<T>(yrow + (int64_t)(ok[u] ? xx : 0) * h.C + cc * EPC);
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int i = i0 + u * 256;
+            Vec16<T> out;
+#pragma unroll
+            for (int e = 0; e < EPC; ++e) out.set(e, ok[u] ? relu_keep_nan(__builtin_fmaf(v[u].get(e), sc[e], sh[e])) : 0.f);
+            if (i < row_chunks) *(Vec16<T>*)(zrow + (int64_t)i * EPC) = out;
+        }
+    }
+}
+
+// backward pass 1: per-block partial sums of dU = dz * (u > 0) and dU * xhat (the layout and the order of bn_bwd_reduce_kernel)
+template <typename T>
+__global__ __launch_bounds__(256) void bn_relu_bwd_reduce_kernel(const T* __restrict__ dz, const T* __restrict__ y,
+                                                                 const float* __restrict__ scale, const float* __restrict__ shift,
+                                                                 const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                                 float* __restrict__ part, int64_t M, int C, int rows_per_block) {
+    constexpr int EPC = Vec16<T>::N;
+    extern __shared__ float red[];  // [2][rpi][C]
+    const int cpp = C / EPC, rpi = 256 / cpp;
+    const int cx = threadIdx.x % cpp, py = threadIdx.x / cpp;
+    float sc[EPC], sh[EPC], mu[EPC], rs[EPC], s1[EPC], s2[EPC];
+#pragma unroll
+    for (int e = 0; e < EPC; ++e) {
+        const int c = cx * EPC + e;
+        sc[e] = scale[c]; sh[e] = shift[c]; mu[e] = mean[c]; rs[e] = rstd[c];
+        s1[e] = s2[e] = 0.f;
+    }
+    const int64_t m0 = (int64_t)blockIdx.x * rows_per_block;
+    int64_t m1 = m0 + rows_per_block;
+    if (m1 > M) m1 = M;
+    for (int64_t m = m0 + py; m < m1; m += rpi) {
+        const Vec16<T> g = *(const Vec16<T>*)(dz + m * C + cx * EPC);
+        const Vec16<T> v = *(const Vec16<T>*)(y + m * C + cx * EPC);
+#pragma unroll
+        for (int e = 0; e < EPC; ++e) {
+            const float yv = v.get(e);
+            const float du = __builtin_fmaf(yv, sc[e], sh[e]) > 0.f ? g.get(e) : 0.f;
+            s1[e] += du;
+            s2[e] += du * (yv - mu[e]) * rs[e];
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < EPC; ++e) {
+        red[(0 * rpi + py) * C + cx * EPC + e] = s1[e];
+        red[(1 * rpi + py) * C + cx * EPC + e] = s2[e];
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < 2 * C; i += 256) {
+        const int which = i / C, c = i - which * C;
+        float s = 0.f;
+        for (int k = 0; k < rpi; ++k) s += red[(which * rpi + k) * C + c];
+        part[((int64_t)blockIdx.x * 2 + which) * C + c] = s;
+    }
+}
+
+// backward pass 2: dY = a * dU + k1 * y + k2 into a halo buffer (coef = fva_bn_bwd_finalize's [3][C] table, packed as in the SiLU pass)
+template <typename T>
+__global__ __launch_bounds__(256) void bn_relu_bwd_apply_kernel(const T* __restrict__ dz, const T* __restrict__ y,
+                                                                const float* __restrict__ scale, const float* __restrict__ shift,
+                                                                const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                                const float* __restrict__ coef, T* __restrict__ dy, const HaloIdx h) {
+    constexpr int EPC = Vec16<T>::N, U = FVA_BN_UNROLL;
+    const int row_chunks = h.Wp * h.cpp;
+    const int cmask = h.cpp - 1, cshift = 31 - __builtin_clz(h.cpp);
+    const int cc = threadIdx.x & cmask;
+    const int row = blockIdx.x, b = row / h.Hp, yy = row - b * h.Hp - h.pad;
+    T* orow = dy + (int64_t)row * row_chunks * EPC;
+    if (yy < 0 || yy >= h.H) {
+        Vec16<T> zero;
+#pragma unroll
+        for (int e = 0; e < EPC; ++e) zero.set(e, 0.f);
+        for (int i = threadIdx.x; i < row_chunks; i += 256) *(Vec16<T>*)(orow + (int64_t)i * EPC) = zero;
+        return;
+    }
+    const int64_t m0 = ((int64_t)b * h.H + yy) * h.W;
+    // fp32 tensors: the three-term sum is formed in double and rounded ONCE (k1 = cb * rstd and k2 = cc - k1 * mean rounded to fp32 first
+    // would each leave 2^-24 of a term that may be larger than the result; v_fma_f64 runs at half the fp32 rate on this chip and the pass
+    // is HBM-bound).  bf16 tensors: fp32 arithmetic, the store's 2^-9 is the error.
+    using K = typename std::conditional<std::is_same<T, float>::value, double, float>::type;
+    float sc[EPC], sh[EPC];
+    K ka[EPC], k1[EPC], k2[EPC];
+#pragma unroll
+    for (int e = 0; e < EPC; ++e) {
+        const int c = cc * EPC + e;
+        sc[e] = scale[c]; sh[e] = shift[c];
+        if constexpr (std::is_same<T, float>::value) {
+            ka[e] = (double)coef[c];
+            k1[e] = (double)coef[h.C + c] * (double)rstd[c];
+            k2[e] = (double)coef[2 * h.C + c] - k1[e] * (double)mean[c];
+        } else {
+            const BnBwdK k = bn_bwd_pack_coef(coef[c], shift[c], mean[c], rstd[c], coef[h.C + c], coef[2 * h.C + c]);
+            ka[e] = k.a; k1[e] = k.k1; k2[e] = k.k2;
+        }
+    }
+    for (int i0 = threadIdx.x; i0 < row_chunks; i0 += 256 * U) {
+        Vec16<T> g[U], v[U];
+        bool ok[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int i = i0 + u * 256;
+            const int xx = (i >> cshift) - h.pad;
+            ok[u] = i < row_chunks && xx >= 0 && xx < h.W;
+            const int64_t off = (m0 + (ok[u] ? xx : 0)) * h.C + cc * EPC;
+            g[u] = ld_last<T>(dz + off);
+            v[u] = ld_last<T>(y + off);
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int i = i0 + u * 256;
+            Vec16<T> out;
+#pragma unroll
+            for (int e = 0; e < EPC; ++e) {
+                const float yv = v[u].get(e);
+                const float du = __builtin_fmaf(yv, sc[e], sh[e]) > 0.f ? g[u].get(e) : 0.f;
+                const K r = ka[e] * (K)du + (k1[e] * (K)yv + k2[e]);
+                out.set(e, ok[u] ? (float)r : 0.f);
+            }
+            if (i < row_chunks) *(Vec16<T>*)(orow + (int64_t)i * EPC) = out;
+        }
+    }
+}
+
+// The convolution bias in front of BatchNorm (vgg.py:43 builds Conv2d(bias=True)): training subtracts it again with the batch mean, so
+// the convolution runs without it; what it leaves is the running mean (it tracks mean(y) + b: running_mean += momentum * b after
+// fva_bn_finalize) and the eval-mode shift, beta + (b - running_mean) * scale.
+__global__ void bn_bias_running_mean_kernel(int C, float* running_mean, const float* __restrict__ bias, float momentum) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c < C) running_mean[c] = __builtin_fmaf(momentum, bias[c], running_mean[c]);
+}
+__global__ void bn_eval_coeffs_bias_kernel(int C, const float* gamma, const float* beta, const float* rm, const float* rv, const float* bias,
+                                           float eps, float* scale, float* shift) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c < C) {
+        const float sc = gamma[c] / sqrtf(rv[c] + eps);
+        scale[c] = sc;
+        shift[c] = beta[c] + (bias[c] - rm[c]) * sc;
+    }
+}
+
+int relu_halo(const char* who, int dtype, int B, int H, int W, int C, int pad, HaloIdx& h) {
+    int rc = check_chan(dtype, C, who);
+    if (rc) return rc;
+    if (B <= 0 || H <= 0 || W <= 0 || pad < 0 || pad > 1) return fva_fail(FVA_ERR_ARG, "%s: bad shape B=%d H=%d W=%d pad=%d", who, B, H, W, pad);
+    h = make_halo(B, H, W, C, pad, dtype == FVA_BF16 ? 8 : 4);
+    if (h.total >= (1ll << 31)) return fva_fail(FVA_ERR_ARG, "%s: tensor too large", who);
+    if ((h.cpp & (h.cpp - 1)) || h.cpp > 256) return fva_fail(FVA_ERR_ARG, "%s: C=%d must be a power of two (<= 256 chunks)", who, C);
+    return FVA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fva_bn_relu_apply(int dtype, const void* y, const float* scale, const float* shift, void* z, int z_pad, int B, int H, int W, int C,
+                      void* stream) {
+    HaloIdx h;
+    const int rc = relu_halo("fva_bn_relu_apply", dtype, B, H, W, C, z_pad, h);
+    if (rc) return rc;
+    if (!y || !scale || !shift || !z) return fva_fail(FVA_ERR_ARG, "fva_bn_relu_apply: null pointer");
+    hipStream_t s = (hipStream_t)stream;
+    if (dtype == FVA_BF16)
+        hipLaunchKernelGGL(bn_relu_apply_kernel<bf16_t>, dim3(B * h.Hp), dim3(256), 0, s, (const bf16_t*)y, scale, shift, (bf16_t*)z, h);
+    else
+        hipLaunchKernelGGL(bn_relu_apply_kernel<float>, dim3(B * h.Hp), dim3(256), 0, s, (const float*)y, scale, shift, (float*)z, h);
+    FVA_LAUNCH_CHECK("bn_relu_apply_kernel");
+    return FVA_OK;
+}
+
+int fva_bn_relu_bwd_reduce(int dtype, const void* dz, const void* y, const float* scale, const float* shift, const float* save_mean,
+                           const float* save_rstd, float* partial, int32_t nblocks, int64_t M, int C, void* stream) {
+    const char* who = "fva_bn_relu_bwd_reduce";
+    const int rc = check_chan(dtype, C, who);
+    if (rc) return rc;
+    const int epc = dtype == FVA_BF16 ? 8 : 4;
+    const int cpp = C / epc;
+    if (cpp > 256 || 256 % cpp) return fva_fail(FVA_ERR_ARG, "%s: C=%d unsupported", who, C);
+    if (!dz || !y || !scale || !shift || !save_mean || !save_rstd || !partial || M <= 0) return fva_fail(FVA_ERR_ARG, "%s: bad argument", who);
+    const int rows = bwd_rows_per_block(M, C, epc);
+    if (nblocks != cdiv(M, rows)) return fva_fail(FVA_ERR_ARG, "%s: nblocks %d != fva_bn_bwd_blocks() = %d", who, nblocks, cdiv(M, rows));
+    const int smem = 2 * (256 / cpp) * C * 4;
+    hipStream_t s = (hipStream_t)stream;
+    if (dtype == FVA_BF16)
+        hipLaunchKernelGGL(bn_relu_bwd_reduce_kernel<bf16_t>, dim3(nblocks), dim3(256), smem, s, (const bf16_t*)dz, (const bf16_t*)y, scale, shift,
+                           save_mean, save_rstd, partial, M, C, rows);
+    else
+        hipLaunchKernelGGL(bn_relu_bwd_reduce_kernel<float>, dim3(nblocks), dim3(256), smem, s, (const float*)dz, (const float*)y, scale, shift,
+                           save_mean, save_rstd, partial, M, C, rows);
+    FVA_LAUNCH_CHECK("bn_relu_bwd_reduce_kernel");
+    return FVA_OK;
+}
+
+int fva_bn_relu_bwd_apply(int dtype, const void* dz, const void* y, const float* scale, const float* shift, const float* save_mean,
+                          const float* save_rstd, const float* coef, void* dy, int dy_pad, int B, int H, int W, int C, void* stream) {
+    HaloIdx h;
+    const int rc = relu_halo("fva_bn_relu_bwd_apply", dtype, B, H, W, C, dy_pad, h);
+    if (rc) return rc;
+    if (!dz || !y || !scale || !shift || !save_mean || !save_rstd || !coef || !dy) return fva_fail(FVA_ERR_ARG, "fva_bn_relu_bwd_apply: null pointer");
+    hipStream_t s = (hipStream_t)stream;
+    if (dtype == FVA_BF16)
+        hipLaunchKernelGGL(bn_relu_bwd_apply_kernel<bf16_t>, dim3(B * h.Hp), dim3(256), 0, s, (const bf16_t*)dz, (const bf16_t*)y, scale, shift,
+                           save_mean, save_rstd, coef, (bf16_t*)dy, h);
+    else
+        hipLaunchKernelGGL(bn_relu_bwd_apply_kernel<float>, dim3(B * h.Hp), dim3(256), 0, s, (const float*)dz, (const float*)y, scale, shift,
+                           save_mean, save_rstd, coef, (float*)dy, h);
+    FVA_LAUNCH_CHECK("bn_relu_bwd_apply_kernel");
+    return FVA_OK;
+}
+
+int fva_bn_bias_running_mean(int32_t C, float* running_mean, const float* bias, float momentum, void* stream) {
+    if (!running_mean || !bias || C <= 0) return fva_fail(FVA_ERR_ARG, "fva_bn_bias_running_mean: bad argument");
+    hipLaunchKernelGGL(bn_bias_running_mean_kernel, dim3(cdiv(C, 256)), dim3(256), 0, (hipStream_t)stream, C, running_mean, bias, momentum);
+    FVA_LAUNCH_CHECK("bn_bias_running_mean_kernel");
+    return FVA_OK;
+}
+
+int fva_bn_eval_coeffs_bias(int32_t C, const float* gamma, const float* beta, const float* rm, const float* rv, const float* bias, float eps,
+                            float* scale, float* shift, void* stream) {
+    if (!gamma || !beta || !rm || !rv || !bias || !scale || !shift || C <= 0) return fva_fail(FVA_ERR_ARG, "fva_bn_eval_coeffs_bias: bad argument");
+    hipLaunchKernelGGL(bn_eval_coeffs_bias_kernel, dim3(cdiv(C, 256)), dim3(256), 0, (hipStream_t)stream, C, gamma, beta, rm, rv, bias, eps,
+                       scale, shift);
+    FVA_LAUNCH_CHECK("bn_eval_coeffs_bias_kernel");
     return FVA_OK;
 }
 

@@ -255,3 +255,136 @@ int fva_top1_accuracy(const void* logits, int logits_dtype, const void* labels, 
 }
 
 }  // extern "C"
+
+// =========================================================================================================
+// nn.AdaptiveAvgPool2d((7, 7)) + torch.flatten(x, 1) of the VGG classifiers (reference classfication/models/vgg.py:27,67-68).
+// Input: halo / dense NHWC [B][H+2p][W+2p][C]; output [B][C*49] in the reference's flatten(NCHW) order (c * 49 + i * 7 + j), in the
+// compute dtype: the operand of the first Linear as stored.  Windows as torch defines them: rows floor(i*H/7) .. ceil((i+1)*H/7), any H, W
+// >= 1 (H < 7 repeats pixels, H % 7 != 0 overlaps).  One block per (image, 64 channels): 16-byte reads along the channel axis, window sums
+// in scan order in fp32, the 64 x 49 tile turned through LDS (row stride 49 floats: odd, conflict-free), and written as ONE contiguous
+// run of 64 * 49 elements with 16-byte stores.  At 7x7 this is a transpose.  Backward in gather form: the block loads its run of the
+// gradient into LDS (divided by the window size), then every input pixel adds the windows that contain it in (i, j) order.  No atomics.
+namespace {
+
+constexpr int P7 = 7, P7_BINS = 49, P7_CB = 64;
+__device__ __forceinline__ int p7_start(int i, int n) { return (i * n) / P7; }
+__device__ __forceinline__ int p7_end(int i, int n) { return ((i + 1) * n + P7 - 1) / P7; }
+
+template <typename T>
+__global__ __launch_bounds__(CLS_THREADS) void pool7_fwd_kernel(const T* __restrict__ x, int pad, int H, int W, int C, T* __restrict__ out) {
+    constexpr int EPC = Vec16<T>::N, CPL = P7_CB / EPC, SLOTS = CLS_THREADS / CPL;
+    __shared__ __attribute__((aligned(16))) float tile[P7_CB * P7_BINS];
+    const int b = blockIdx.y, c0 = blockIdx.x * P7_CB;
+    const int nch = C - c0 < P7_CB ? C - c0 : P7_CB;              // channels of this block (a multiple of EPC)
+    const int chunk = threadIdx.x % CPL, slot = threadIdx.x / CPL;
+    const int Wp = W + 2 * pad;
+    const T* xb = x + ((int64_t)b * (H + 2 * pad) * Wp) * C + c0 + chunk * EPC;
+    if (chunk * EPC < nch) {
+        for (int bin = slot; bin < P7_BINS; bin += SLOTS) {
+            const int i = bin / P7, j = bin - i * P7;
+            const int h0 = p7_start(i, H), h1 = p7_end(i, H), w0 = p7_start(j, W), w1 = p7_end(j, W);
+            float acc[EPC];
+#pragma unroll
+            for (int e = 0; e < EPC; ++e) acc[e] = 0.f;
+            for (int hh = h0; hh < h1; ++hh)
+                for (int ww = w0; ww < w1; ++ww) {
+                    const Vec16<T> v = *(const Vec16<T>*)(xb + ((int64_t)(hh + pad) * Wp + (ww + pad)) * C);
+#pragma unroll
+                    for (int e = 0; e < EPC; ++e) acc[e] += v.get(e);
+                }
+            const float cnt = (float)((h1 - h0) * (w1 - w0));
+#pragma unroll
+            for (int e = 0; e < EPC; ++e) tile[(chunk * EPC + e) * P7_BINS + bin] = acc[e] / cnt;
+        }
+    }
+    __syncthreads();
+    T* ob = out + ((int64_t)b * C + c0) * P7_BINS;                // 16-byte aligned: (b * C + c0) * 49 elements, C and c0 multiples of EPC
+    const int nvec = nch * P7_BINS / EPC;
+    for (int v = threadIdx.x; v < nvec; v += CLS_THREADS) {
+        Vec16<T> o;
+#pragma unroll
+        for (int e = 0; e < EPC; ++e) o.set(e, tile[v * EPC + e]);
+        *(Vec16<T>*)(ob + (int64_t)v * EPC) = o;
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(CLS_THREADS) void pool7_bwd_kernel(const T* __restrict__ g, int H, int W, int C, T* __restrict__ dx) {
+    constexpr int EPC = Vec16<T>::N, CPL = P7_CB / EPC, SLOTS = CLS_THREADS / CPL;
+    __shared__ __attribute__((aligned(16))) float tile[P7_CB * P7_BINS];
+    const int b = blockIdx.y, c0 = blockIdx.x * P7_CB;
+    const int nch = C - c0 < P7_CB ? C - c0 : P7_CB;
+    const T* gb = g + ((int64_t)b * C + c0) * P7_BINS;
+    const int nvec = nch * P7_BINS / EPC;
+    for (int v = threadIdx.x; v < nvec; v += CLS_THREADS) {
+        const Vec16<T> q = *(const Vec16<T>*)(gb + (int64_t)v * EPC);
+#pragma unroll
+        for (int e = 0; e < EPC; ++e) {
+            const int bin = (v * EPC + e) % P7_BINS, i = bin / P7, j = bin - i * P7;
+            const float cnt = (float)((p7_end(i, H) - p7_start(i, H)) * (p7_end(j, W) - p7_start(j, W)));
+            tile[v * EPC + e] = q.get(e) / cnt;
+        }
+    }
+    __syncthreads();
+    const int chunk = threadIdx.x % CPL, slot = threadIdx.x / CPL;
+    if (chunk * EPC >= nch) return;
+    for (int pix = slot; pix < H * W; pix += SLOTS) {
+        const int hh = pix / W, ww = pix - hh * W;
+        float acc[EPC];
+#pragma unroll
+        for (int e = 0; e < EPC; ++e) acc[e] = 0.f;
+        for (int i = 0; i < P7; ++i) {
+            if (hh < p7_start(i, H) || hh >= p7_end(i, H)) continue;
+            for (int j = 0; j < P7; ++j) {
+                if (ww < p7_start(j, W) || ww >= p7_end(j, W)) continue;
+#pragma unroll
+                for (int e = 0; e < EPC; ++e) acc[e] += tile[(chunk * EPC + e) * P7_BINS + i * P7 + j];
+            }
+        }
+        Vec16<T> o;
+#pragma unroll
+        for (int e = 0; e < EPC; ++e) o.set(e, acc[e]);
+        *(Vec16<T>*)(dx + (((int64_t)b * H + hh) * W + ww) * C + c0 + chunk * EPC) = o;
+    }
+}
+
+int pool7_check(const char* who, int dtype, int B, int H, int W, int C) {
+    if (dtype != FVA_F32 && dtype != FVA_BF16) return fva_fail(FVA_ERR_ARG, "%s: bad dtype %d", who, dtype);
+    const int epc = dtype == FVA_BF16 ? 8 : 4;
+    if (B < 1 || H < 1 || W < 1 || C < 1 || B > 65535 || H > 4096 || W > 4096 || C % epc)
+        return fva_fail(FVA_ERR_ARG, "%s: bad shape B=%d H=%d W=%d C=%d (C must be a multiple of %d, B <= 65535, H, W <= 4096)", who, B, H, W, C, epc);
+    return FVA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fva_adaptive_avgpool7_fwd(int dtype, const void* x, int x_pad, int B, int H, int W, int C, void* out, void* stream) {
+    if (!x || !out) return fva_fail(FVA_ERR_ARG, "fva_adaptive_avgpool7_fwd: null pointer");
+    const int rc = pool7_check("fva_adaptive_avgpool7_fwd", dtype, B, H, W, C);
+    if (rc) return rc;
+    if (x_pad < 0 || x_pad > 1) return fva_fail(FVA_ERR_ARG, "fva_adaptive_avgpool7_fwd: bad pad %d", x_pad);
+    const dim3 grid((C + P7_CB - 1) / P7_CB, B);
+    if (dtype == FVA_BF16)
+        hipLaunchKernelGGL(pool7_fwd_kernel<bf16_t>, grid, dim3(CLS_THREADS), 0, (hipStream_t)stream, (const bf16_t*)x, x_pad, H, W, C, (bf16_t*)out);
+    else
+        hipLaunchKernelGGL(pool7_fwd_kernel<float>, grid, dim3(CLS_THREADS), 0, (hipStream_t)stream, (const float*)x, x_pad, H, W, C, (float*)out);
+    FVA_LAUNCH_CHECK("pool7_fwd_kernel");
+    return FVA_OK;
+}
+
+int fva_adaptive_avgpool7_bwd(int dtype, const void* g, int B, int H, int W, int C, void* dx, void* stream) {
+    if (!g || !dx) return fva_fail(FVA_ERR_ARG, "fva_adaptive_avgpool7_bwd: null pointer");
+    const int rc = pool7_check("fva_adaptive_avgpool7_bwd", dtype, B, H, W, C);
+    if (rc) return rc;
+    const dim3 grid((C + P7_CB - 1) / P7_CB, B);
+    if (dtype == FVA_BF16)
+        hipLaunchKernelGGL(pool7_bwd_kernel<bf16_t>, grid, dim3(CLS_THREADS), 0, (hipStream_t)stream, (const bf16_t*)g, H, W, C, (bf16_t*)dx);
+    else
+        hipLaunchKernelGGL(pool7_bwd_kernel<float>, grid, dim3(CLS_THREADS), 0, (hipStream_t)stream, (const float*)g, H, W, C, (float*)dx);
+    FVA_LAUNCH_CHECK("pool7_bwd_kernel");
+    return FVA_OK;
+}
+
+}  // extern "C"

@@ -261,3 +261,130 @@ int fva_maxpool2_bwd(int dtype, const void* dz, const void* x, int x_pad, void* 
 }
 
 }  // extern "C"
+
+// =========================================================================================================
+// nn.Dropout of the VGG classifiers (reference classfication/models/vgg.py:32,35) over rows [R][N] in the compute dtype:
+// out = x * keep * scale, scale = 1 / (1 - p).  The random bits are Philox-4x32-10 (Salmon, Moraes, Dror, Shaw: "Parallel random numbers:
+// as easy as 1, 2, 3", SC'11), counter-based: key = the seed's two halves, counter = (element index / 4, 0, call counter's two halves),
+// and element k takes word k % 4 of its group -- the mask of an element depends on (seed, call counter, element index) and nothing else
+// (not on the dtype, the grid or the vector width).  keep = word >= p * 2^32.
+// The state lives in DEVICE memory, int64 state[4] = {seed, call counter, blocks finished, unused}: thread 0 of every block reads seed and
+// counter and hands them to its block through LDS; when a block is done it adds 1 to state[2] (an integer atomic), and the block that
+// finds itself last -- every other block has read the counter by then -- advances the call counter and returns state[2] to zero.  So a
+// captured graph draws a new mask on every replay, and the host never reads anything back.
+// The mask is not stored.  Backward: dx = dout * scale where out != 0 (fva_dropout_bwd).  After a ReLU that is exact: a kept element
+// with x = 0 has a gradient that the ReLU's own backward mask discards anyway.
+namespace {
+
+struct Philox4 {
+    uint32_t v[4];
+};
+__device__ __forceinline__ Philox4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+        const uint32_t n0 = hi1 ^ c1 ^ k0, n2 = hi0 ^ c3 ^ k1;
+        c0 = n0; c1 = lo1; c2 = n2; c3 = lo0;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    return Philox4{{c0, c1, c2, c3}};
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void dropout_fwd_kernel(const T* __restrict__ x, T* __restrict__ out, int64_t nvec, uint32_t threshold, float scale,
+                                                          long long* state) {
+    constexpr int EPC = Vec16<T>::N;
+    __shared__ long long st[2];
+    if (threadIdx.x == 0) {
+        st[0] = state[0];
+        st[1] = state[1];
+    }
+    __syncthreads();
+    const uint32_t k0 = (uint32_t)st[0], k1 = (uint32_t)((unsigned long long)st[0] >> 32);
+    const uint32_t n0 = (uint32_t)st[1], n1 = (uint32_t)((unsigned long long)st[1] >> 32);
+    for (int64_t v = blockIdx.x * (int64_t)256 + threadIdx.x; v < nvec; v += (int64_t)gridDim.x * 256) {
+        const Vec16<T> in = *(const Vec16<T>*)(x + v * EPC);
+        Vec16<T> o;
+#pragma unroll
+        for (int q = 0; q < EPC / 4; ++q) {
+            const Philox4 r = philox4x32_10((uint32_t)(v * (EPC / 4) + q), 0u, n0, n1, k0, k1);       // group index < 2^32: checked by the host
+#pragma unroll
+            for (int e = 0; e < 4; ++e) o.set(q * 4 + e, r.v[e] >= threshold ? in.get(q * 4 + e) * scale : 0.f);
+        }
+        *(Vec16<T>*)(out + v * EPC) = o;
+    }
+    __syncthreads();                    // thread 0 has read the state (it handed it out above); the block's work is issued
+    if (threadIdx.x == 0) {
+        const unsigned long long done = atomicAdd((unsigned long long*)&state[2], 1ull);
+        if (done == (unsigned long long)gridDim.x - 1) {          // the last block: nobody reads the counter any more
+            state[1] = st[1] + 1;
+            state[2] = 0;
+        }
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void dropout_bwd_kernel(const T* __restrict__ dout, const T* __restrict__ out, T* __restrict__ dx, int64_t nvec,
+                                                          float scale) {
+    constexpr int EPC = Vec16<T>::N;
+    for (int64_t v = blockIdx.x * (int64_t)256 + threadIdx.x; v < nvec; v += (int64_t)gridDim.x * 256) {
+        const Vec16<T> g = *(const Vec16<T>*)(dout + v * EPC), z = *(const Vec16<T>*)(out + v * EPC);
+        Vec16<T> o;
+#pragma unroll
+        for (int e = 0; e < EPC; ++e) o.set(e, z.get(e) != 0.f ? g.get(e) * scale : 0.f);
+        *(Vec16<T>*)(dx + v * EPC) = o;
+    }
+}
+
+int dropout_check(const char* who, int dtype, int64_t n, float p) {
+    if (dtype != FVA_F32 && dtype != FVA_BF16) return fva_fail(FVA_ERR_ARG, "%s: bad dtype %d", who, dtype);
+    const int epc = dtype == FVA_BF16 ? 8 : 4;
+    if (n < 1 || n % epc || n / 4 >= (1ll << 32)) return fva_fail(FVA_ERR_ARG, "%s: n = %lld must be a positive multiple of %d below 2^34", who, (long long)n, epc);
+    if (!(p > 0.f && p < 1.f)) return fva_fail(FVA_ERR_ARG, "%s: p = %g outside (0, 1) (p = 0 is the identity: launch nothing)", who, (double)p);
+    return FVA_OK;
+}
+inline int dropout_grid(int64_t nvec) {
+    const int64_t g = (nvec + 255) / 256;
+    return (int)(g > 2048 ? 2048 : g);
+}
+
+}  // namespace
+
+extern "C" {
+
+int fva_dropout_fwd(int dtype, const void* x, void* out, int64_t n, float p, int64_t* state, void* stream) {
+    const int rc = dropout_check("fva_dropout_fwd", dtype, n, p);
+    if (rc) return rc;
+    if (!x || !out || !state) return fva_fail(FVA_ERR_ARG, "fva_dropout_fwd: null pointer");
+    const double t = (double)p * 4294967296.0;
+    const uint32_t threshold = t >= 4294967295.0 ? 4294967295u : (uint32_t)t;
+    const float scale = (float)(1.0 / (1.0 - (double)p));
+    const int64_t nvec = n / (dtype == FVA_BF16 ? 8 : 4);
+    hipStream_t s = (hipStream_t)stream;
+    if (dtype == FVA_BF16)
+        hipLaunchKernelGGL(dropout_fwd_kernel<bf16_t>, dim3(dropout_grid(nvec)), dim3(256), 0, s, (const bf16_t*)x, (bf16_t*)out, nvec, threshold, scale,
+                           (long long*)state);
+    else
+        hipLaunchKernelGGL(dropout_fwd_kernel<float>, dim3(dropout_grid(nvec)), dim3(256), 0, s, (const float*)x, (float*)out, nvec, threshold, scale,
+                           (long long*)state);
+    FVA_LAUNCH_CHECK("dropout_fwd_kernel");
+    return FVA_OK;
+}
+
+int fva_dropout_bwd(int dtype, const void* dout, const void* out, void* dx, int64_t n, float p, void* stream) {
+    const int rc = dropout_check("fva_dropout_bwd", dtype, n, p);
+    if (rc) return rc;
+    if (!dout || !out || !dx) return fva_fail(FVA_ERR_ARG, "fva_dropout_bwd: null pointer");
+    const float scale = (float)(1.0 / (1.0 - (double)p));
+    const int64_t nvec = n / (dtype == FVA_BF16 ? 8 : 4);
+    hipStream_t s = (hipStream_t)stream;
+    if (dtype == FVA_BF16)
+        hipLaunchKernelGGL(dropout_bwd_kernel<bf16_t>, dim3(dropout_grid(nvec)), dim3(256), 0, s, (const bf16_t*)dout, (const bf16_t*)out, (bf16_t*)dx, nvec, scale);
+    else
+        hipLaunchKernelGGL(dropout_bwd_kernel<float>, dim3(dropout_grid(nvec)), dim3(256), 0, s, (const float*)dout, (const float*)out, (float*)dx, nvec, scale);
+    FVA_LAUNCH_CHECK("dropout_bwd_kernel");
+    return FVA_OK;
+}
+
+}  // extern "C"

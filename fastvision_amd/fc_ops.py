@@ -7,6 +7,7 @@ The reference's Fast head runs RoI features through the VGG classifier ``Linear(
     linear_relu(x, lin)        relu(x @ W^T + b): a 1x1 convolution over R "pixels" on the implicit-GEMM kernel with the bias + ReLU
                                epilogue (fva_conv_fwd_bias_act); backward: ReLU mask + bias gradient in one pass
                                (fva_rows_relu_bwd + fva_colsum), then fva_conv_dgrad / fva_conv_wgrad
+    dropout(x, drop, state)    nn.Dropout behind a ReLU: counter-based mask drawn on the device (fva_dropout_fwd), no stored mask
     linear(x, lin)             x @ W^T + b without activation, fp32 output: the detection head's biased 1x1 convolution (ops.HeadFn)
     cross_entropy_mean / focal_mean / smooth_l1_mean      value and gradient in one launch (fva_row_loss / fva_smooth_l1)
 
@@ -20,7 +21,7 @@ import torch
 from . import _lib
 from .ops import HeadFn, _code, _p, _stream, get_compute_dtype, packed_weights, require_gpu
 
-__all__ = ['linear_relu', 'linear', 'cross_entropy_mean', 'focal_mean', 'smooth_l1_mean']
+__all__ = ['linear_relu', 'dropout', 'new_dropout_state', 'linear', 'cross_entropy_mean', 'focal_mean', 'smooth_l1_mean']
 
 
 def _packed_linear(weight, d, dtype):
@@ -84,6 +85,63 @@ def linear_relu(x, lin, dtype=None):
     if lin.bias is None or lin.in_features % bk or lin.out_features % 8:
         raise RuntimeError(f'linear_relu: in_features must be a multiple of {bk}, out_features of 8, with a bias')
     return LinearReLUFn.apply(x, lin.weight, lin.bias, dtype)
+
+
+def rows_as(x, dtype):
+    """x [R, N] (fp32 or bf16, any strides) as a contiguous tensor of ``dtype``: itself when it already is one, else converted by the
+    library's strided pack kernel (fva_pack_nchw with R images of N channels and one pixel) -- no ATen cast or copy kernel."""
+    if x.dtype == dtype and x.is_contiguous():
+        return x
+    if x.dim() != 2 or x.dtype not in (torch.float32, torch.bfloat16):
+        raise RuntimeError(f'fastvision_amd: expected a [rows, features] fp32 / bf16 tensor, got {tuple(x.shape)} {x.dtype}')
+    out = torch.empty(x.shape, dtype=dtype, device=x.device)
+    _lib.call('fva_pack_nchw', _code(dtype), _p(x), 1 if x.dtype == torch.bfloat16 else 0, x.stride(0), x.stride(1), 0, 0, _p(out), 0,
+              x.shape[0], x.shape[1], 1, 1, _stream())
+    return out
+
+
+class DropoutFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, p, state, dtype):
+        require_gpu(x, 'dropout')
+        xs = rows_as(x.detach(), dtype)
+        out = torch.empty_like(xs)
+        _lib.call('fva_dropout_fwd', _code(dtype), _p(xs), _p(out), xs.numel(), p, _p(state), _stream())
+        ctx.save_for_backward(out)
+        ctx.p, ctx.dtype, ctx.x_dtype = p, dtype, x.dtype
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        dtype = ctx.dtype
+        g = rows_as(g, dtype)
+        dx = torch.empty_like(g)
+        _lib.call('fva_dropout_bwd', _code(dtype), _p(g), _p(ctx.saved_tensors[0]), _p(dx), g.numel(), ctx.p, _stream())
+        return rows_as(dx, ctx.x_dtype), None, None, None
+
+
+def new_dropout_state(seed=None):
+    """int64[4] = {seed, call counter, 0, 0}: the generator state of ``dropout`` (a CPU tensor; move it with the model).  ``seed`` defaults
+    to ``torch.initial_seed()``, the value of the last ``torch.manual_seed`` -- read, not drawn, so building a model consumes nothing of
+    torch's random stream and the parameter initialisation stays the reference's."""
+    seed = torch.initial_seed() if seed is None else int(seed)
+    return torch.tensor([seed & 0x7FFFFFFFFFFFFFFF, 0, 0, 0], dtype=torch.int64)
+
+
+def dropout(x, drop, state, dtype=None):
+    """``drop(x)`` for an ``nn.Dropout`` that FOLLOWS A RELU (x >= 0); ``drop.p`` and ``drop.training`` are read at call time.  Eval mode
+    and p = 0 return ``x`` itself and launch nothing.  ``state``: a device tensor from ``new_dropout_state`` that every call advances on
+    the device (Philox-4x32-10 keyed by seed, call counter and element index); the mask is not stored -- backward reads it off
+    ``out != 0``, which behind a ReLU loses only gradients that the ReLU's own mask discards."""
+    p = float(drop.p)
+    if not drop.training or p == 0.0:
+        return x
+    require_gpu(x, 'dropout')
+    if p >= 1.0:
+        raise RuntimeError('dropout: p = 1 is not on this path')
+    if state.dtype != torch.int64 or state.numel() != 4 or not state.is_cuda:
+        raise RuntimeError('dropout: state must be the int64[4] device tensor of new_dropout_state()')
+    return DropoutFn.apply(x, p, state, dtype or get_compute_dtype())
 
 
 def linear(x, lin, dtype=None):

@@ -634,6 +634,43 @@ int fva_softmax_ce(const float* logits, const void* labels, int label_dtype, con
 int fva_top1_accuracy(const void* logits, int logits_dtype, const void* labels, int label_dtype, int32_t R, int32_t C, float* out,
                       void* workspace, void* stream);
 
+/* ---- VGG classifiers (classfication/models/vgg.py:24-48: Conv2d(bias) -> BatchNorm2d -> ReLU blocks, AdaptiveAvgPool2d((7, 7)) + flatten,
+ * Dropout) -----------------------------------------------------------------------------------------------------------------------
+ * BatchNorm + ReLU, the three streaming passes of the SiLU path with the activation exchanged (table form: the statistics come from
+ * fva_conv_fwd + fva_bn_finalize, the backward sums go through fva_bn_bwd_finalize; C / (16-byte chunk) a power of two <= 256):
+ *   fva_bn_relu_apply       z = max(0, y * scale + shift) from the dense convolution output y [B*H*W][C] into the halo buffer
+ *                           z [B][H+2p][W+2p][C], zero border included (p = z_pad, 0 or 1).  A NaN stays a NaN.
+ *   fva_bn_relu_bwd_reduce  partial [fva_bn_bwd_blocks()][2][C] = per-block sums of dU = dz * (u > 0) and dU * xhat, u = y * scale +
+ *                           shift recomputed from y (never from the rounded z), xhat = (y - mean) * rstd.  Fixed order, no atomics.
+ *   fva_bn_relu_bwd_apply   dy = a * dU + k1 * y + k2 (= gamma * rstd * (dU - dbeta / n - xhat * dgamma / n); coef = the [3][C] table of
+ *                           fva_bn_bwd_finalize) as a halo buffer with zero border: the operand of fva_conv_dgrad / fva_conv_wgrad.
+ * The convolution bias in front of BatchNorm cancels in z in training mode, so the convolution runs without it; it stays visible in two
+ * places: running_mean tracks mean(y) + b (fva_bn_bias_running_mean: running_mean += momentum * b, after fva_bn_finalize) and in eval mode
+ * it folds into the shift (fva_bn_eval_coeffs_bias: scale = gamma / sqrt(running_var + eps), shift = beta + (b - running_mean) * scale). */
+int fva_bn_relu_apply(int dtype, const void* y, const float* scale, const float* shift, void* z, int z_pad, int B, int H, int W, int C,
+                      void* stream);
+int fva_bn_relu_bwd_reduce(int dtype, const void* dz, const void* y, const float* scale, const float* shift, const float* save_mean,
+                           const float* save_rstd, float* partial, int32_t nblocks, int64_t M, int C, void* stream);
+int fva_bn_relu_bwd_apply(int dtype, const void* dz, const void* y, const float* scale, const float* shift, const float* save_mean,
+                          const float* save_rstd, const float* coef, void* dy, int dy_pad, int B, int H, int W, int C, void* stream);
+int fva_bn_bias_running_mean(int32_t C, float* running_mean, const float* bias, float momentum, void* stream);
+int fva_bn_eval_coeffs_bias(int32_t C, const float* gamma, const float* beta, const float* rm, const float* rv, const float* bias, float eps,
+                            float* scale, float* shift, void* stream);
+/* nn.AdaptiveAvgPool2d((7, 7)) + torch.flatten(x, 1).  x: NHWC [B][H+2*x_pad][W+2*x_pad][C] of dtype; out [B][C*49] of dtype in the
+ * order c * 49 + i * 7 + j; windows floor(i*H/7) .. ceil((i+1)*H/7) as torch defines them, any H, W >= 1; C a multiple of the 16-byte
+ * chunk.  Backward (gather form, no atomics): g [B][C*49] of dtype -> dx dense NHWC [B][H][W][C] of dtype.  One launch each;
+ * run-to-run bit-identical. */
+int fva_adaptive_avgpool7_fwd(int dtype, const void* x, int x_pad, int B, int H, int W, int C, void* out, void* stream);
+int fva_adaptive_avgpool7_bwd(int dtype, const void* g, int B, int H, int W, int C, void* dx, void* stream);
+/* nn.Dropout over n contiguous elements of dtype (n a multiple of the 16-byte chunk): out = x * keep / (1 - p), 0 < p < 1 (p = 0 and eval
+ * mode are the identity: the caller launches nothing).  keep comes from Philox-4x32-10 keyed by (seed, call counter, element index);
+ * state = int64[4] in DEVICE memory: {seed, call counter, 0, 0}.  The launch reads seed and counter and advances the counter itself
+ * (word 2 is its block count, zero between launches), so a captured graph draws a new mask on every replay without the host.
+ * All launches that share one state must be on ONE stream (or ordered by events): a launch reads the counter its predecessor wrote.
+ * No mask is stored: fva_dropout_bwd gives dx = dout / (1 - p) where out != 0, else 0 (exact behind a ReLU). */
+int fva_dropout_fwd(int dtype, const void* x, void* out, int64_t n, float p, int64_t* state, void* stream);
+int fva_dropout_bwd(int dtype, const void* dout, const void* out, void* dx, int64_t n, float p, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
