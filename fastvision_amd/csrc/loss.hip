@@ -654,8 +654,9 @@ __global__ __launch_bounds__(256) void row_loss_kernel(const float* __restrict__
         const float q = 1.f - p;
         const float qg = powf(q, gamma);
         loss = -qg * logp;
-        // d/dp [-(1-p)^g log p] * p, with d p / d z_k = p (delta - s_k)
-        dldlogp = (gamma * powf(q, gamma - 1.f) * logp - qg / p) * p;
+        // d/dp [-(1-p)^g log p] * p, with d p / d z_k = p (delta - s_k); multiplied out, so that a label whose probability underflows to 0
+        // (its logit about 104 below the row's maximum) gives -1 and not (-inf) * 0 = NaN
+        dldlogp = gamma * powf(q, gamma - 1.f) * logp * p - qg;
     }
     row_loss[r] = loss;
     if (grad) {
