@@ -1,12 +1,13 @@
-// BatchNorm2d (train/eval) + SiLU (+ residual add) forward and backward, and the FPN upsample/concat and
-// layout helpers, for gfx950.  All of these are HBM-bound streaming kernels: 16 bytes per lane, channels
+// BatchNorm2d (train/eval) + activation (SiLU with an optional residual add, or ReLU) forward and backward, and the FPN upsample/concat
+// and layout helpers, for gfx950.  All of these are HBM-bound streaming kernels: 16 bytes per lane, channels
 // contiguous (NHWC), no LDS except for the per-block channel reductions.
 //
 // Algorithmic bytes per element (bf16): apply = 2 (y) + 2 (z) [+2 residual]; backward pass 1 = 4 (dz, y);
 // backward pass 2 = 4 + 2 (dy).
 //
 // Replaces nn.BatchNorm2d / nn.SiLU / `identity + conv2` (reference classfication/models/darknet53.py:11-17,
-// 28-31, 58-62) and nn.Upsample + torch.cat (detection/neck/yolov3neck.py:71,105,110).
+// 28-31, 58-62), Conv2d(bias) -> BatchNorm2d -> ReLU (classfication/models/vgg.py:39-48) and nn.Upsample + torch.cat
+// (detection/neck/yolov3neck.py:71,105,110).
 #include <type_traits>
 
 #include "common.h"
@@ -199,15 +200,66 @@ __global__ __launch_bounds__(256) void bn_acc_finalize_kernel(const BnFwdAcc fin
     if (threadIdx.x == 0 && fin.nbt) *fin.nbt += 1;
 }
 
+// The activation behind the BatchNorm is a compile-time policy of the three streaming passes (apply, backward reduce, backward apply): one
+// kernel per pass, instantiated for SiLU (Darknet-53 / YOLOv3; plain and accumulator forms, with a residual) and for ReLU (the VGG `_bn`
+// classifiers, reference classfication/models/vgg.py:39-48; plain table form only).  A policy gives
+//   fwd(y, sc, sh)       z from one element of the convolution output
+//   du(dz, y, sc, sh)    dU = dz * act'(u) for the reduce pass; u = y * sc + sh is recomputed from y in both backward passes (the stored z
+//                        is rounded: z == 0 and u > 0 can disagree)
+//   Coef<T>, pack<T>, dy the per-channel coefficients of the backward apply pass and dY = a * dU + k1 * y + k2 formed from them
+struct ActSiLU {
+    template <typename T> using Coef = BnBwdK;
+    static __device__ __forceinline__ float fwd(float y, float sc, float sh) { return bn_silu_fwd_elem(y, sc, sh); }
+    static __device__ __forceinline__ float du(float dz, float y, float sc, float sh) { return dz * silu_grad(y * sc + sh); }
+    template <typename T>
+    static __device__ __forceinline__ BnBwdK pack(float a, float shift, float mean, float rstd, float coef_b, float coef_c) {
+        return bn_bwd_pack_coef(a, shift, mean, rstd, coef_b, coef_c);
+    }
+    static __device__ __forceinline__ float dy(float dz, float y, float sc, const BnBwdK& k) { return bn_bwd_apply_elem(dz, y, sc, k.sh, k.a, k.k1, k.k2); }
+};
+// fp32 tensors: ReLU's three-term sum is formed in double and rounded ONCE (k1 = cb * rstd and k2 = cc - k1 * mean rounded to fp32 first
+// would each leave 2^-24 of a term that may be larger than the result; v_fma_f64 runs at half the fp32 rate on this chip and the pass
+// is HBM-bound).  bf16 tensors: fp32 arithmetic, the store's 2^-9 is the error.
+struct BnBwdKd {
+    float sh;
+    double a, k1, k2;
+};
+struct ActReLU {
+    template <typename T> using Coef = typename std::conditional<std::is_same<T, float>::value, BnBwdKd, BnBwdK>::type;
+    static __device__ __forceinline__ float fwd(float y, float sc, float sh) {
+        const float u = __builtin_fmaf(y, sc, sh);
+        return u <= 0.f ? 0.f : u;       // a NaN stays a NaN, as in torch.relu
+    }
+    static __device__ __forceinline__ float du(float dz, float y, float sc, float sh) { return __builtin_fmaf(y, sc, sh) > 0.f ? dz : 0.f; }
+    template <typename T>
+    static __device__ __forceinline__ Coef<T> pack(float a, float shift, float mean, float rstd, float coef_b, float coef_c) {
+        if constexpr (std::is_same<T, float>::value) {
+            BnBwdKd k;
+            k.sh = shift;
+            k.a = (double)a;
+            k.k1 = (double)coef_b * (double)rstd;
+            k.k2 = (double)coef_c - k.k1 * (double)mean;
+            return k;
+        } else {
+            return bn_bwd_pack_coef(a, shift, mean, rstd, coef_b, coef_c);
+        }
+    }
+    template <typename K>
+    static __device__ __forceinline__ float dy(float dz, float y, float sc, const K& k) {
+        using F = decltype(k.a);
+        return (float)(k.a * (F)du(dz, y, sc, k.sh) + (k.k1 * (F)y + k.k2));
+    }
+};
+
 // One padded row of z per block and step (grid = rows for the plain form; the accumulator form runs at most 2048 blocks that walk the rows,
 // so that its prologue is paid once per block).  FIN: scale / shift come from the layer's accumulator -- all C channels once per block,
 // C / 256 per thread, through LDS (dynamic: 2 C floats), while the first row's loads are already in flight; block 0 also writes them out
 // for the backward pass, updates the running statistics and returns the OTHER direction's accumulator to zero (its own one is still being
 // read by the other blocks: the layer's backward pass zeroes that).
-template <typename T, bool FIN>
-__global__ __launch_bounds__(256) void bn_silu_apply_kernel(const T* __restrict__ y, const float* __restrict__ scale,
-                                                            const float* __restrict__ shift, const T* __restrict__ res,
-                                                            int res_pad, T* __restrict__ z, const HaloIdx h, const BnFwdAcc fin, int nrows) {
+template <typename Act, typename T, bool FIN>
+__global__ __launch_bounds__(256) void bn_apply_kernel(const T* __restrict__ y, const float* __restrict__ scale,
+                                                       const float* __restrict__ shift, const T* __restrict__ res,
+                                                       int res_pad, T* __restrict__ z, const HaloIdx h, const BnFwdAcc fin, int nrows) {
     constexpr int EPC = Vec16<T>::N, U = FVA_BN_UNROLL;
     extern __shared__ float fx_tab[];          // FIN: [2][C]
     const int row_chunks = h.Wp * h.cpp;
@@ -300,7 +352,7 @@ __global__ __launch_bounds__(256) void bn_silu_apply_kernel(const T* __restrict_
                 Vec16<T> out;
 #pragma unroll
                 for (int e = 0; e < EPC; ++e) {
-                    float o = bn_silu_fwd_elem(v[u].get(e), sc[e], sh[e]);
+                    float o = Act::fwd(v[u].get(e), sc[e], sh[e]);
                     if (has_res) o += r[u].get(e);
                     out.set(e, ok[u] ? o : 0.f);
                 }
@@ -311,7 +363,7 @@ __global__ __launch_bounds__(256) void bn_silu_apply_kernel(const T* __restrict_
 }
 
 // backward pass 1: per-channel partial sums of dU and dU*xhat.  threads = (channel chunk, pixel row group)
-template <typename T>
+template <typename Act, typename T>
 __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const T* __restrict__ dz, const T* __restrict__ y,
                                                             const float* __restrict__ scale, const float* __restrict__ shift,
                                                             const float* __restrict__ mean, const float* __restrict__ rstd,
@@ -336,7 +388,7 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const T* __restrict_
 #pragma unroll
         for (int e = 0; e < EPC; ++e) {
             const float yv = v.get(e);
-            const float du = g.get(e) * silu_grad(yv * sc[e] + sh[e]);
+            const float du = Act::du(g.get(e), yv, sc[e], sh[e]);
             s1[e] += du;
             s2[e] += du * (yv - mu[e]) * rs[e];
         }
@@ -395,7 +447,7 @@ __global__ __launch_bounds__(1024) void bn_bwd_finalize_kernel(const float* __re
 // FIN: dgamma, dbeta and the three coefficients come from the layer's backward accumulator (the sums the dgrad epilogues / the reduce
 // pass added), all C channels once per block through LDS (dynamic: 5 C floats); block 0 writes dgamma / dbeta and returns the layer's
 // FORWARD accumulator to zero (fin.zero) -- nobody reads that one any more; its own is zeroed by the layer's next forward pass.
-template <typename T, bool FIN>
+template <typename Act, typename T, bool FIN>
 __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const T* __restrict__ dz, const T* __restrict__ y,
                                                            const float* __restrict__ scale, const float* __restrict__ shift,
                                                            const float* __restrict__ mean, const float* __restrict__ rstd,
@@ -407,7 +459,10 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const T* __restrict__
     const int cmask = h.cpp - 1, cshift = 31 - __builtin_clz(h.cpp);
     // lane-constant channel chunk (cpp divides 256): dY = a*dU + k1*y + k2 with k1 = coefB*rstd, k2 = coefC - k1*mean
     const int cc = threadIdx.x & cmask;
-    float sc[EPC], sh[EPC], ka[EPC], k1[EPC], k2[EPC];
+    using K = typename Act::template Coef<T>;
+    static_assert(!FIN || std::is_same<K, BnBwdK>::value, "the accumulator form keeps its coefficients as floats in LDS");
+    float sc[EPC];
+    K k[EPC];
     Vec16<T> g[U], v[U];
     bool ok[U];
     int64_t m0 = 0;
@@ -439,12 +494,12 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const T* __restrict__
             if (fin.replicas > 1) fx_value2(fx_from_lds(fx_words, h.C, c), s1, s2);
             else fx_load2(fin.acc, h.C, 1, c, s1, s2);
             const BnBwdCoef q = bn_bwd_coef(s1, s2, fin.n, fin.gamma[c], rstd[c]);
-            const BnBwdK k = bn_bwd_pack_coef(q.a, shift[c], mean[c], rstd[c], q.cb, q.cc);
+            const BnBwdK p = bn_bwd_pack_coef(q.a, shift[c], mean[c], rstd[c], q.cb, q.cc);
             fx_tab[c] = scale[c];
-            fx_tab[h.C + c] = k.sh;
-            fx_tab[2 * h.C + c] = k.a;
-            fx_tab[3 * h.C + c] = k.k1;
-            fx_tab[4 * h.C + c] = k.k2;
+            fx_tab[h.C + c] = p.sh;
+            fx_tab[2 * h.C + c] = p.a;
+            fx_tab[3 * h.C + c] = p.k1;
+            fx_tab[4 * h.C + c] = p.k2;
             if (writer) {
                 fin.dbeta[c] = fin.accumulate ? fin.dbeta[c] + q.dbeta : q.dbeta;
                 fin.dgamma[c] = fin.accumulate ? fin.dgamma[c] + q.dgamma : q.dgamma;
@@ -455,18 +510,14 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const T* __restrict__
 #pragma unroll
         for (int e = 0; e < EPC; ++e) {
             const int c = cc * EPC + e;
-            sc[e] = fx_tab[c]; sh[e] = fx_tab[h.C + c]; ka[e] = fx_tab[2 * h.C + c]; k1[e] = fx_tab[3 * h.C + c]; k2[e] = fx_tab[4 * h.C + c];
+            sc[e] = fx_tab[c]; k[e].sh = fx_tab[h.C + c]; k[e].a = fx_tab[2 * h.C + c]; k[e].k1 = fx_tab[3 * h.C + c]; k[e].k2 = fx_tab[4 * h.C + c];
         }
     } else {
 #pragma unroll
         for (int e = 0; e < EPC; ++e) {
             const int c = cc * EPC + e;
-            const BnBwdK k = bn_bwd_pack_coef(coef[c], shift[c], mean[c], rstd[c], coef[h.C + c], coef[2 * h.C + c]);
+            k[e] = Act::template pack<T>(coef[c], shift[c], mean[c], rstd[c], coef[h.C + c], coef[2 * h.C + c]);
             sc[e] = scale[c];
-            sh[e] = k.sh;
-            ka[e] = k.a;
-            k1[e] = k.k1;
-            k2[e] = k.k2;
         }
     }
     // one padded row per block and step
@@ -489,7 +540,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const T* __restrict__
                 Vec16<T> out;
 #pragma unroll
                 for (int e = 0; e < EPC; ++e) {
-                    out.set(e, ok[u] ? bn_bwd_apply_elem(g[u].get(e), v[u].get(e), sc[e], sh[e], ka[e], k1[e], k2[e]) : 0.f);
+                    out.set(e, ok[u] ? Act::dy(g[u].get(e), v[u].get(e), sc[e], k[e]) : 0.f);
                 }
                 if (i < row_chunks) *(Vec16<T>*)(orow + (int64_t)i * EPC) = out;
             }
@@ -610,6 +661,128 @@ inline int stream_grid(int64_t items) {
     return (int)g;
 }
 
+// ---- argument checks and launches shared by the entry points below
+int check_chan(int dtype, int C, const char* who) {
+    if (dtype != FVA_F32 && dtype != FVA_BF16) return fva_fail(FVA_ERR_ARG, "%s: bad dtype", who);
+    const int epc = dtype == FVA_BF16 ? 8 : 4;
+    if (C <= 0 || C % epc) return fva_fail(FVA_ERR_ARG, "%s: C=%d not a multiple of %d", who, C, epc);
+    return FVA_OK;
+}
+
+int fill_fwd_acc(const fva_bn_fwd_acc* a, int64_t M, BnFwdAcc& f, const char* who) {
+    if (!a || !a->acc || !a->gamma || !a->beta || !a->save_mean || !a->save_rstd || !a->scale || !a->shift)
+        return fva_fail(FVA_ERR_ARG, "%s: null pointer in the accumulator descriptor", who);
+    if (a->zero == a->acc) return fva_fail(FVA_ERR_ARG, "%s: `zero` must be another accumulator (this one is still being read)", who);
+    if (!fva_replicas_ok(a->replicas)) return fva_fail(FVA_ERR_ARG, "%s: replicas = %d is not a power of two in 1..%d", who, a->replicas, FVA_BN_ACC_MAX_REPLICAS);
+    f.acc = (long long*)a->acc; f.zero = (long long*)a->zero; f.replicas = a->replicas; f.gamma = a->gamma; f.beta = a->beta;
+    f.running_mean = a->running_mean; f.running_var = a->running_var; f.nbt = (long long*)a->num_batches_tracked;
+    f.momentum = a->momentum; f.eps = a->eps; f.n = bn_n((double)M);
+    f.save_mean = a->save_mean; f.save_rstd = a->save_rstd; f.scale = a->scale; f.shift = a->shift;
+    return FVA_OK;
+}
+
+// f(T()) with T = bf16_t or float, as `dtype` says (check_chan has refused every other code)
+template <typename F>
+void by_dtype(int dtype, F&& f) {
+    if (dtype == FVA_BF16) f(bf16_t());
+    else f(float());
+}
+
+// the HaloIdx of an apply pass, checked; `strict` (the ReLU entries) also refuses an empty shape and a pad other than 0 / 1
+int checked_halo(const char* who, int dtype, int B, int H, int W, int C, int pad, bool strict, HaloIdx& h) {
+    if (strict && (B <= 0 || H <= 0 || W <= 0 || pad < 0 || pad > 1)) return fva_fail(FVA_ERR_ARG, "%s: bad shape B=%d H=%d W=%d pad=%d", who, B, H, W, pad);
+    h = make_halo(B, H, W, C, pad, dtype == FVA_BF16 ? 8 : 4);
+    if (h.total >= (1ll << 31)) return fva_fail(FVA_ERR_ARG, "%s: tensor too large", who);
+    if ((h.cpp & (h.cpp - 1)) || h.cpp > 256) return fva_fail(FVA_ERR_ARG, "%s: C=%d must be a power of two (<= 256 chunks)", who, C);
+    return FVA_OK;
+}
+
+// FIN: the accumulator form (scale / shift come out of `acc`); otherwise the plain form, one block per padded row
+template <typename Act, bool FIN>
+int apply_impl(const char* who, int dtype, const void* y, const float* scale, const float* shift, const fva_bn_fwd_acc* acc, const void* residual,
+               int res_pad, void* z, int z_pad, int B, int H, int W, int C, void* stream) {
+    int rc = check_chan(dtype, C, who);
+    if (rc) return rc;
+    if (!y || !z || (!FIN && (!scale || !shift))) return fva_fail(FVA_ERR_ARG, "%s: null pointer", who);
+    BnFwdAcc f = BnFwdAcc();
+    if (FIN && (rc = fill_fwd_acc(acc, (int64_t)B * H * W, f, who))) return rc;
+    HaloIdx h;
+    if ((rc = checked_halo(who, dtype, B, H, W, C, z_pad, std::is_same<Act, ActReLU>::value, h))) return rc;
+    const int nrows = B * h.Hp, grid = FIN && nrows > ACC_GRID ? ACC_GRID : nrows;
+    const int smem = FIN ? 2 * C * 4 + (f.replicas > 1 ? FX_WORDS * C * 8 : 0) : 0;
+    by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((bn_apply_kernel<Act, T, FIN>), dim3(grid), dim3(256), smem, (hipStream_t)stream, (const T*)y, scale, shift,
+                           (const T*)residual, res_pad, (T*)z, h, f, nrows);
+    });
+    FVA_LAUNCH_CHECK(FIN ? "bn_apply_kernel<acc>" : "bn_apply_kernel");
+    return FVA_OK;
+}
+
+int bwd_rows_per_block(int64_t M, int C, int epc) {
+    const int rpi = 256 / (C / epc) > 0 ? 256 / (C / epc) : 1;
+    int64_t rows = (M + 2047) / 2048;           // at most 2048 blocks
+    if (rows < (int64_t)rpi * 8) rows = (int64_t)rpi * 8;
+    rows = (rows + rpi - 1) / rpi * rpi;
+    return (int)rows;
+}
+
+template <typename Act>
+int bwd_reduce_impl(const char* who, int dtype, const void* dz, const void* y, const float* scale, const float* shift,
+                    const float* save_mean, const float* save_rstd, float* partial, int64_t* acc, int replicas, int32_t nblocks, int64_t M, int C,
+                    void* stream) {
+    constexpr bool relu = std::is_same<Act, ActReLU>::value;      // its entry also refuses M <= 0 and words two refusals in its own way
+    int rc = check_chan(dtype, C, who);
+    if (acc && !fva_replicas_ok(replicas)) return fva_fail(FVA_ERR_ARG, "%s: replicas = %d is not a power of two in 1..%d", who, replicas, FVA_BN_ACC_MAX_REPLICAS);
+    if (rc) return rc;
+    const int epc = dtype == FVA_BF16 ? 8 : 4;
+    const int cpp = C / epc;
+    if (cpp > 256 || 256 % cpp) return fva_fail(FVA_ERR_ARG, "%s: C=%d unsupported", who, C);
+    if (!dz || !y || !scale || !shift || !save_mean || !save_rstd || (!partial && !acc) || (relu && M <= 0))
+        return fva_fail(FVA_ERR_ARG, relu ? "%s: bad argument" : "%s: null pointer", who);
+    const int rows = bwd_rows_per_block(M, C, epc);
+    if (acc) nblocks = cdiv(M, rows);
+    if (nblocks != cdiv(M, rows))
+        return fva_fail(FVA_ERR_ARG, relu ? "%s: nblocks %d != fva_bn_bwd_blocks() = %d" : "%s: nblocks %d != %d", who, nblocks, cdiv(M, rows));
+    const int smem = 2 * (256 / cpp) * C * 4;
+    by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((bn_bwd_reduce_kernel<Act, T>), dim3(nblocks), dim3(256), smem, (hipStream_t)stream, (const T*)dz, (const T*)y, scale,
+                           shift, save_mean, save_rstd, partial, (long long*)acc, replicas, M, C, rows);
+    });
+    FVA_LAUNCH_CHECK("bn_bwd_reduce_kernel");
+    return FVA_OK;
+}
+
+// FIN: the accumulator form (`a`, at most ACC_GRID blocks that walk the rows); otherwise `coef`, one block per padded row
+template <typename Act, bool FIN>
+int bwd_apply_impl(const char* who, int dtype, const void* dz, const void* y, const float* scale, const float* shift, const float* save_mean,
+                   const float* save_rstd, const float* coef, const fva_bn_bwd_acc* a, void* dy, int dy_pad, int B, int H, int W, int C,
+                   void* stream) {
+    int rc = check_chan(dtype, C, who);
+    if (rc) return rc;
+    if (!dz || !y || !scale || !shift || !save_mean || !save_rstd || (!coef && !a) || !dy) return fva_fail(FVA_ERR_ARG, "%s: null pointer", who);
+    HaloIdx h;
+    if ((rc = checked_halo(who, dtype, B, H, W, C, dy_pad, std::is_same<Act, ActReLU>::value, h))) return rc;
+    BnBwdAcc f = BnBwdAcc();
+    if (FIN) {
+        if (!a->acc || !a->gamma || !a->dgamma || !a->dbeta) return fva_fail(FVA_ERR_ARG, "%s: null pointer in the accumulator descriptor", who);
+        if (a->zero == a->acc) return fva_fail(FVA_ERR_ARG, "%s: `zero` must be another accumulator (this one is still being read)", who);
+        if (!fva_replicas_ok(a->replicas)) return fva_fail(FVA_ERR_ARG, "%s: replicas = %d is not a power of two in 1..%d", who, a->replicas, FVA_BN_ACC_MAX_REPLICAS);
+        f.acc = (long long*)a->acc; f.zero = (long long*)a->zero; f.replicas = a->replicas; f.gamma = a->gamma; f.dgamma = a->dgamma; f.dbeta = a->dbeta;
+        f.accumulate = a->accumulate; f.n = bn_n((double)B * H * W);
+    }
+    const int nrows = B * h.Hp, grid = FIN && nrows > ACC_GRID ? ACC_GRID : nrows;
+    const int smem = FIN ? (5 * C + (C & 1)) * 4 + (f.replicas > 1 ? FX_WORDS * C * 8 : 0) : 0;
+    by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((bn_bwd_apply_kernel<Act, T, FIN>), dim3(grid), dim3(256), smem, (hipStream_t)stream, (const T*)dz, (const T*)y, scale, shift,
+                           save_mean, save_rstd, coef, (T*)dy, h, nrows, f);
+    });
+    FVA_LAUNCH_CHECK(FIN ? "bn_bwd_apply_kernel<acc>" : "bn_bwd_apply_kernel");
+    return FVA_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -654,44 +827,6 @@ int fva_bn_eval_coeffs(int32_t C, const float* gamma, const float* beta, const f
     return FVA_OK;
 }
 
-static int check_chan(int dtype, int C, const char* who) {
-    if (dtype != FVA_F32 && dtype != FVA_BF16) return fva_fail(FVA_ERR_ARG, "%s: bad dtype", who);
-    const int epc = dtype == FVA_BF16 ? 8 : 4;
-    if (C <= 0 || C % epc) return fva_fail(FVA_ERR_ARG, "%s: C=%d not a multiple of %d", who, C, epc);
-    return FVA_OK;
-}
-
-int fva_bn_silu_apply(int dtype, const void* y, const float* scale, const float* shift, const void* residual, int res_pad,
-                      void* z, int z_pad, int B, int H, int W, int C, void* stream) {
-    int rc = check_chan(dtype, C, "fva_bn_silu_apply");
-    if (rc) return rc;
-    if (!y || !scale || !shift || !z) return fva_fail(FVA_ERR_ARG, "fva_bn_silu_apply: null pointer");
-    const HaloIdx h = make_halo(B, H, W, C, z_pad, dtype == FVA_BF16 ? 8 : 4);
-    if (h.total >= (1ll << 31)) return fva_fail(FVA_ERR_ARG, "fva_bn_silu_apply: tensor too large");
-    if ((h.cpp & (h.cpp - 1)) || h.cpp > 256) return fva_fail(FVA_ERR_ARG, "fva_bn_silu_apply: C=%d must be a power of two (<= 256 chunks)", C);
-    hipStream_t s = (hipStream_t)stream;
-    if (dtype == FVA_BF16)
-        hipLaunchKernelGGL((bn_silu_apply_kernel<bf16_t, false>), dim3(B * h.Hp), dim3(256), 0, s, (const bf16_t*)y, scale, shift,
-                           (const bf16_t*)residual, res_pad, (bf16_t*)z, h, BnFwdAcc(), B * h.Hp);
-    else
-        hipLaunchKernelGGL((bn_silu_apply_kernel<float, false>), dim3(B * h.Hp), dim3(256), 0, s, (const float*)y, scale, shift,
-                           (const float*)residual, res_pad, (float*)z, h, BnFwdAcc(), B * h.Hp);
-    FVA_LAUNCH_CHECK("bn_silu_apply_kernel");
-    return FVA_OK;
-}
-
-static int fill_fwd_acc(const fva_bn_fwd_acc* a, int64_t M, BnFwdAcc& f, const char* who) {
-    if (!a || !a->acc || !a->gamma || !a->beta || !a->save_mean || !a->save_rstd || !a->scale || !a->shift)
-        return fva_fail(FVA_ERR_ARG, "%s: null pointer in the accumulator descriptor", who);
-    if (a->zero == a->acc) return fva_fail(FVA_ERR_ARG, "%s: `zero` must be another accumulator (this one is still being read)", who);
-    if (!fva_replicas_ok(a->replicas)) return fva_fail(FVA_ERR_ARG, "%s: replicas = %d is not a power of two in 1..%d", who, a->replicas, FVA_BN_ACC_MAX_REPLICAS);
-    f.acc = (long long*)a->acc; f.zero = (long long*)a->zero; f.replicas = a->replicas; f.gamma = a->gamma; f.beta = a->beta;
-    f.running_mean = a->running_mean; f.running_var = a->running_var; f.nbt = (long long*)a->num_batches_tracked;
-    f.momentum = a->momentum; f.eps = a->eps; f.n = bn_n((double)M);
-    f.save_mean = a->save_mean; f.save_rstd = a->save_rstd; f.scale = a->scale; f.shift = a->shift;
-    return FVA_OK;
-}
-
 int fva_bn_acc_finalize(const fva_bn_fwd_acc* acc, int64_t M, int C, void* stream) {
     BnFwdAcc f = BnFwdAcc();
     const int rc = fill_fwd_acc(acc, M, f, "fva_bn_acc_finalize");
@@ -703,35 +838,19 @@ int fva_bn_acc_finalize(const fva_bn_fwd_acc* acc, int64_t M, int C, void* strea
     return FVA_OK;
 }
 
-int fva_bn_silu_apply_acc(int dtype, const void* y, const fva_bn_fwd_acc* acc, const void* residual, int res_pad, void* z, int z_pad, int B,
-                          int H, int W, int C, void* stream) {
-    int rc = check_chan(dtype, C, "fva_bn_silu_apply_acc");
-    if (rc) return rc;
-    if (!y || !z) return fva_fail(FVA_ERR_ARG, "fva_bn_silu_apply_acc: null pointer");
-    BnFwdAcc f = BnFwdAcc();
-    rc = fill_fwd_acc(acc, (int64_t)B * H * W, f, "fva_bn_silu_apply_acc");
-    if (rc) return rc;
-    const HaloIdx h = make_halo(B, H, W, C, z_pad, dtype == FVA_BF16 ? 8 : 4);
-    if (h.total >= (1ll << 31)) return fva_fail(FVA_ERR_ARG, "fva_bn_silu_apply_acc: tensor too large");
-    if ((h.cpp & (h.cpp - 1)) || h.cpp > 256) return fva_fail(FVA_ERR_ARG, "fva_bn_silu_apply_acc: C=%d must be a power of two (<= 256 chunks)", C);
-    hipStream_t s = (hipStream_t)stream;
-    const int nrows = B * h.Hp, grid = nrows < ACC_GRID ? nrows : ACC_GRID, smem = 2 * C * 4 + (f.replicas > 1 ? FX_WORDS * C * 8 : 0);
-    if (dtype == FVA_BF16)
-        hipLaunchKernelGGL((bn_silu_apply_kernel<bf16_t, true>), dim3(grid), dim3(256), smem, s, (const bf16_t*)y, nullptr, nullptr,
-                           (const bf16_t*)residual, res_pad, (bf16_t*)z, h, f, nrows);
-    else
-        hipLaunchKernelGGL((bn_silu_apply_kernel<float, true>), dim3(grid), dim3(256), smem, s, (const float*)y, nullptr, nullptr,
-                           (const float*)residual, res_pad, (float*)z, h, f, nrows);
-    FVA_LAUNCH_CHECK("bn_silu_apply_kernel<acc>");
-    return FVA_OK;
+int fva_bn_silu_apply(int dtype, const void* y, const float* scale, const float* shift, const void* residual, int res_pad,
+                      void* z, int z_pad, int B, int H, int W, int C, void* stream) {
+    return apply_impl<ActSiLU, false>("fva_bn_silu_apply", dtype, y, scale, shift, nullptr, residual, res_pad, z, z_pad, B, H, W, C, stream);
 }
 
-static int bwd_rows_per_block(int64_t M, int C, int epc) {
-    const int rpi = 256 / (C / epc) > 0 ? 256 / (C / epc) : 1;
-    int64_t rows = (M + 2047) / 2048;           // at most 2048 blocks
-    if (rows < (int64_t)rpi * 8) rows = (int64_t)rpi * 8;
-    rows = (rows + rpi - 1) / rpi * rpi;
-    return (int)rows;
+int fva_bn_silu_apply_acc(int dtype, const void* y, const fva_bn_fwd_acc* acc, const void* residual, int res_pad, void* z, int z_pad, int B,
+                          int H, int W, int C, void* stream) {
+    return apply_impl<ActSiLU, true>("fva_bn_silu_apply_acc", dtype, y, nullptr, nullptr, acc, residual, res_pad, z, z_pad, B, H, W, C, stream);
+}
+
+int fva_bn_relu_apply(int dtype, const void* y, const float* scale, const float* shift, void* z, int z_pad, int B, int H, int W, int C,
+                      void* stream) {
+    return apply_impl<ActReLU, false>("fva_bn_relu_apply", dtype, y, scale, shift, nullptr, nullptr, 0, z, z_pad, B, H, W, C, stream);
 }
 
 int32_t fva_bn_bwd_blocks(int dtype, int64_t M, int C) {
@@ -740,42 +859,22 @@ int32_t fva_bn_bwd_blocks(int dtype, int64_t M, int C) {
     return cdiv(M, bwd_rows_per_block(M, C, epc));
 }
 
-static int bwd_reduce_impl(const char* who, int dtype, const void* dz, const void* y, const float* scale, const float* shift,
-                           const float* save_mean, const float* save_rstd, float* partial, int64_t* acc, int replicas, int32_t nblocks, int64_t M, int C,
-                           void* stream) {
-    int rc = check_chan(dtype, C, who);
-    if (acc && !fva_replicas_ok(replicas)) return fva_fail(FVA_ERR_ARG, "%s: replicas = %d is not a power of two in 1..%d", who, replicas, FVA_BN_ACC_MAX_REPLICAS);
-    if (rc) return rc;
-    const int epc = dtype == FVA_BF16 ? 8 : 4;
-    const int cpp = C / epc;
-    if (cpp > 256 || 256 % cpp) return fva_fail(FVA_ERR_ARG, "%s: C=%d unsupported", who, C);
-    if (!dz || !y || !scale || !shift || !save_mean || !save_rstd || (!partial && !acc)) return fva_fail(FVA_ERR_ARG, "%s: null pointer", who);
-    const int rows = bwd_rows_per_block(M, C, epc);
-    if (acc) nblocks = cdiv(M, rows);
-    if (nblocks != cdiv(M, rows)) return fva_fail(FVA_ERR_ARG, "%s: nblocks %d != %d", who, nblocks, cdiv(M, rows));
-    const int smem = 2 * (256 / cpp) * C * 4;
-    hipStream_t s = (hipStream_t)stream;
-    if (dtype == FVA_BF16)
-        hipLaunchKernelGGL(bn_bwd_reduce_kernel<bf16_t>, dim3(nblocks), dim3(256), smem, s, (const bf16_t*)dz, (const bf16_t*)y, scale,
-                           shift, save_mean, save_rstd, partial, (long long*)acc, replicas, M, C, rows);
-    else
-        hipLaunchKernelGGL(bn_bwd_reduce_kernel<float>, dim3(nblocks), dim3(256), smem, s, (const float*)dz, (const float*)y, scale,
-                           shift, save_mean, save_rstd, partial, (long long*)acc, replicas, M, C, rows);
-    FVA_LAUNCH_CHECK("bn_bwd_reduce_kernel");
-    return FVA_OK;
-}
-
 int fva_bn_silu_bwd_reduce(int dtype, const void* dz, const void* y, const float* scale, const float* shift,
                            const float* save_mean, const float* save_rstd, float* partial, int32_t nblocks, int64_t M, int C,
                            void* stream) {
     if (!partial) return fva_fail(FVA_ERR_ARG, "fva_bn_silu_bwd_reduce: null pointer");
-    return bwd_reduce_impl("fva_bn_silu_bwd_reduce", dtype, dz, y, scale, shift, save_mean, save_rstd, partial, nullptr, 1, nblocks, M, C, stream);
+    return bwd_reduce_impl<ActSiLU>("fva_bn_silu_bwd_reduce", dtype, dz, y, scale, shift, save_mean, save_rstd, partial, nullptr, 1, nblocks, M, C, stream);
 }
 
 int fva_bn_silu_bwd_reduce_acc(int dtype, const void* dz, const void* y, const float* scale, const float* shift,
                                const float* save_mean, const float* save_rstd, int64_t* acc, int32_t replicas, int64_t M, int C, void* stream) {
     if (!acc) return fva_fail(FVA_ERR_ARG, "fva_bn_silu_bwd_reduce_acc: null pointer");
-    return bwd_reduce_impl("fva_bn_silu_bwd_reduce_acc", dtype, dz, y, scale, shift, save_mean, save_rstd, nullptr, acc, replicas, 0, M, C, stream);
+    return bwd_reduce_impl<ActSiLU>("fva_bn_silu_bwd_reduce_acc", dtype, dz, y, scale, shift, save_mean, save_rstd, nullptr, acc, replicas, 0, M, C, stream);
+}
+
+int fva_bn_relu_bwd_reduce(int dtype, const void* dz, const void* y, const float* scale, const float* shift, const float* save_mean,
+                           const float* save_rstd, float* partial, int32_t nblocks, int64_t M, int C, void* stream) {
+    return bwd_reduce_impl<ActReLU>("fva_bn_relu_bwd_reduce", dtype, dz, y, scale, shift, save_mean, save_rstd, partial, nullptr, 1, nblocks, M, C, stream);
 }
 
 int fva_bn_bwd_finalize(float* partial, int32_t nblocks, int32_t partial_rows, int64_t M, int C, const float* gamma, const float* save_rstd,
@@ -803,54 +902,21 @@ int fva_bn_bwd_finalize(float* partial, int32_t nblocks, int32_t partial_rows, i
     return FVA_OK;
 }
 
-static int bwd_apply_impl(const char* who, int dtype, const void* dz, const void* y, const float* scale, const float* shift, const float* save_mean,
-                          const float* save_rstd, const float* coef, const fva_bn_bwd_acc* a, void* dy, int dy_pad, int B, int H, int W, int C,
-                          void* stream) {
-    int rc = check_chan(dtype, C, who);
-    if (rc) return rc;
-    if (!dz || !y || !scale || !shift || !save_mean || !save_rstd || (!coef && !a) || !dy) return fva_fail(FVA_ERR_ARG, "%s: null pointer", who);
-    const HaloIdx h = make_halo(B, H, W, C, dy_pad, dtype == FVA_BF16 ? 8 : 4);
-    if (h.total >= (1ll << 31)) return fva_fail(FVA_ERR_ARG, "%s: tensor too large", who);
-    if ((h.cpp & (h.cpp - 1)) || h.cpp > 256) return fva_fail(FVA_ERR_ARG, "%s: C=%d must be a power of two (<= 256 chunks)", who, C);
-    hipStream_t s = (hipStream_t)stream;
-    const int nrows = B * h.Hp;
-    if (a) {
-        if (!a->acc || !a->gamma || !a->dgamma || !a->dbeta) return fva_fail(FVA_ERR_ARG, "%s: null pointer in the accumulator descriptor", who);
-        if (a->zero == a->acc) return fva_fail(FVA_ERR_ARG, "%s: `zero` must be another accumulator (this one is still being read)", who);
-        BnBwdAcc f = BnBwdAcc();
-        if (!fva_replicas_ok(a->replicas)) return fva_fail(FVA_ERR_ARG, "%s: replicas = %d is not a power of two in 1..%d", who, a->replicas, FVA_BN_ACC_MAX_REPLICAS);
-        f.acc = (long long*)a->acc; f.zero = (long long*)a->zero; f.replicas = a->replicas; f.gamma = a->gamma; f.dgamma = a->dgamma; f.dbeta = a->dbeta;
-        f.accumulate = a->accumulate; f.n = bn_n((double)B * H * W);
-        const int grid = nrows < ACC_GRID ? nrows : ACC_GRID, smem = (5 * C + (C & 1)) * 4 + (f.replicas > 1 ? FX_WORDS * C * 8 : 0);
-        if (dtype == FVA_BF16)
-            hipLaunchKernelGGL((bn_bwd_apply_kernel<bf16_t, true>), dim3(grid), dim3(256), smem, s, (const bf16_t*)dz, (const bf16_t*)y,
-                               scale, shift, save_mean, save_rstd, nullptr, (bf16_t*)dy, h, nrows, f);
-        else
-            hipLaunchKernelGGL((bn_bwd_apply_kernel<float, true>), dim3(grid), dim3(256), smem, s, (const float*)dz, (const float*)y,
-                               scale, shift, save_mean, save_rstd, nullptr, (float*)dy, h, nrows, f);
-        FVA_LAUNCH_CHECK("bn_bwd_apply_kernel<acc>");
-        return FVA_OK;
-    }
-    if (dtype == FVA_BF16)
-        hipLaunchKernelGGL((bn_bwd_apply_kernel<bf16_t, false>), dim3(nrows), dim3(256), 0, s, (const bf16_t*)dz, (const bf16_t*)y,
-                           scale, shift, save_mean, save_rstd, coef, (bf16_t*)dy, h, nrows, BnBwdAcc());
-    else
-        hipLaunchKernelGGL((bn_bwd_apply_kernel<float, false>), dim3(nrows), dim3(256), 0, s, (const float*)dz, (const float*)y,
-                           scale, shift, save_mean, save_rstd, coef, (float*)dy, h, nrows, BnBwdAcc());
-    FVA_LAUNCH_CHECK("bn_bwd_apply_kernel");
-    return FVA_OK;
-}
-
 int fva_bn_silu_bwd_apply(int dtype, const void* dz, const void* y, const float* scale, const float* shift, const float* save_mean,
                           const float* save_rstd, const float* coef, void* dy, int dy_pad, int B, int H, int W, int C, void* stream) {
     if (!coef) return fva_fail(FVA_ERR_ARG, "fva_bn_silu_bwd_apply: null pointer");
-    return bwd_apply_impl("fva_bn_silu_bwd_apply", dtype, dz, y, scale, shift, save_mean, save_rstd, coef, nullptr, dy, dy_pad, B, H, W, C, stream);
+    return bwd_apply_impl<ActSiLU, false>("fva_bn_silu_bwd_apply", dtype, dz, y, scale, shift, save_mean, save_rstd, coef, nullptr, dy, dy_pad, B, H, W, C, stream);
 }
 
 int fva_bn_silu_bwd_apply_acc(int dtype, const void* dz, const void* y, const float* scale, const float* shift, const float* save_mean,
                               const float* save_rstd, const fva_bn_bwd_acc* acc, void* dy, int dy_pad, int B, int H, int W, int C, void* stream) {
     if (!acc) return fva_fail(FVA_ERR_ARG, "fva_bn_silu_bwd_apply_acc: null pointer");
-    return bwd_apply_impl("fva_bn_silu_bwd_apply_acc", dtype, dz, y, scale, shift, save_mean, save_rstd, nullptr, acc, dy, dy_pad, B, H, W, C, stream);
+    return bwd_apply_impl<ActSiLU, true>("fva_bn_silu_bwd_apply_acc", dtype, dz, y, scale, shift, save_mean, save_rstd, nullptr, acc, dy, dy_pad, B, H, W, C, stream);
+}
+
+int fva_bn_relu_bwd_apply(int dtype, const void* dz, const void* y, const float* scale, const float* shift, const float* save_mean,
+                          const float* save_rstd, const float* coef, void* dy, int dy_pad, int B, int H, int W, int C, void* stream) {
+    return bwd_apply_impl<ActReLU, false>("fva_bn_relu_bwd_apply", dtype, dz, y, scale, shift, save_mean, save_rstd, coef, nullptr, dy, dy_pad, B, H, W, C, stream);
 }
 
 int fva_upsample2_concat_fwd(int dtype, const void* up, int up_pad, const void* skip, int skip_pad, void* out, int B, int h, int w,
@@ -930,172 +996,7 @@ int fva_cast_nhwc(const void* src, int src_dtype, int src_pad, void* dst, int ds
 
 }  // extern "C"
 
-// =========================================================================================================
-// BatchNorm2d + ReLU (reference classfication/models/vgg.py:39-48, `Conv2d(bias=True) -> BatchNorm2d -> ReLU`): the three streaming
-// passes of the SiLU path with the activation exchanged, as kernels of their own (the SiLU kernels above are untouched: same bits).
-// Table form only (fva_conv_fwd's statistics table + fva_bn_finalize / fva_bn_bwd_finalize).  Same shapes of access: one block per padded
-// row, a lane keeps its 16-byte channel chunk for the whole row, FVA_BN_UNROLL chunks in flight, inputs read non-temporal, the zero
-// border written by the pass itself, no atomics.  Bytes per element (bf16): apply 2 + 2; backward pass 1: 4; pass 2: 4 + 2.
-// u = y * scale + shift is recomputed from y in the backward passes (the stored z is rounded: z == 0 and u > 0 can disagree).
 namespace {
-
-__device__ __forceinline__ float relu_keep_nan(float u) { return u <= 0.f ? 0.f : u; }       // a NaN stays a NaN, as in torch.relu
-
-template <typename T>
-__global__ __launch_bounds__(256) void bn_relu_apply_kernel(const T* __restrict__ y, const float* __restrict__ scale,
-                                                            const float* __restrict__ shift, T* __restrict__ z, const HaloIdx h) {
-    constexpr int EPC = Vec16<T>::N, U = FVA_BN_UNROLL;
-    const int row_chunks = h.Wp * h.cpp;
-    const int cmask = h.cpp - 1, cshift = 31 - __builtin_clz(h.cpp);
-    const int cc = threadIdx.x & cmask;
-    const int row = blockIdx.x, b = row / h.Hp, yy = row - b * h.Hp - h.pad;
-    T* zrow = z + (int64_t)row * row_chunks * EPC;
-    if (yy < 0 || yy >= h.H) {          // a border row: zeros (block-uniform branch)
-        Vec16<T> zero;
-#pragma unroll
-        for (int e = 0; e < EPC; ++e) zero.set(e, 0.f);
-        for (int i = threadIdx.x; i < row_chunks; i += 256) *(Vec16<T>*)(zrow + (int64_t)i * EPC) = zero;
-        return;
-    }
-    const T* yrow = y + ((int64_t)b * h.H + yy) * h.W * h.C;
-    float sc[EPC], sh[EPC];
-#pragma unroll
-    for (int e = 0; e < EPC; ++e) {
-        sc[e] = scale[cc * EPC + e];
-        sh[e] = shift[cc * EPC + e];
-    }
-    for (int i0 = threadIdx.x; i0 < row_chunks; i0 += 256 * U) {
-        Vec16<T> v[U];
-        bool ok[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {       // masked chunks read a clamped address (pixel 0 of the row) and store zeros
-            const int i = i0 + u * 256;
-            const int xx = (i >> cshift) - h.pad;
-            ok[u] = i < row_chunks && xx >= 0 && xx < h.W;
-            v[u] = ld_last<T>(yrow + (int64_t)(ok[u] ? xx : 0) * h.C + cc * EPC);
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int i = i0 + u * 256;
-            Vec16<T> out;
-#pragma unroll
-            for (int e = 0; e < EPC; ++e) out.set(e, ok[u] ? relu_keep_nan(__builtin_fmaf(v[u].get(e), sc[e], sh[e])) : 0.f);
-            if (i < row_chunks) *(Vec16<T>*)(zrow + (int64_t)i * EPC) = out;
-        }
-    }
-}
-
-// backward pass 1: per-block partial sums of dU = dz * (u > 0) and dU * xhat (the layout and the order of bn_bwd_reduce_kernel)
-template <typename T>
-__global__ __launch_bounds__(256) void bn_relu_bwd_reduce_kernel(const T* __restrict__ dz, const T* __restrict__ y,
-                                                                 const float* __restrict__ scale, const float* __restrict__ shift,
-                                                                 const float* __restrict__ mean, const float* __restrict__ rstd,
-                                                                 float* __restrict__ part, int64_t M, int C, int rows_per_block) {
-    constexpr int EPC = Vec16<T>::N;
-    extern __shared__ float red[];  // [2][rpi][C]
-    const int cpp = C / EPC, rpi = 256 / cpp;
-    const int cx = threadIdx.x % cpp, py = threadIdx.x / cpp;
-    float sc[EPC], sh[EPC], mu[EPC], rs[EPC], s1[EPC], s2[EPC];
-#pragma unroll
-    for (int e = 0; e < EPC; ++e) {
-        const int c = cx * EPC + e;
-        sc[e] = scale[c]; sh[e] = shift[c]; mu[e] = mean[c]; rs[e] = rstd[c];
-        s1[e] = s2[e] = 0.f;
-    }
-    const int64_t m0 = (int64_t)blockIdx.x * rows_per_block;
-    int64_t m1 = m0 + rows_per_block;
-    if (m1 > M) m1 = M;
-    for (int64_t m = m0 + py; m < m1; m += rpi) {
-        const Vec16<T> g = *(const Vec16<T>*)(dz + m * C + cx * EPC);
-        const Vec16<T> v = *(const Vec16<T>*)(y + m * C + cx * EPC);
-#pragma unroll
-        for (int e = 0; e < EPC; ++e) {
-            const float yv = v.get(e);
-            const float du = __builtin_fmaf(yv, sc[e], sh[e]) > 0.f ? g.get(e) : 0.f;
-            s1[e] += du;
-            s2[e] += du * (yv - mu[e]) * rs[e];
-        }
-    }
-#pragma unroll
-    for (int e = 0; e < EPC; ++e) {
-        red[(0 * rpi + py) * C + cx * EPC + e] = s1[e];
-        red[(1 * rpi + py) * C + cx * EPC + e] = s2[e];
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < 2 * C; i += 256) {
-        const int which = i / C, c = i - which * C;
-        float s = 0.f;
-        for (int k = 0; k < rpi; ++k) s += red[(which * rpi + k) * C + c];
-        part[((int64_t)blockIdx.x * 2 + which) * C + c] = s;
-    }
-}
-
-// backward pass 2: dY = a * dU + k1 * y + k2 into a halo buffer (coef = fva_bn_bwd_finalize's [3][C] table, packed as in the SiLU pass)
-template <typename T>
-__global__ __launch_bounds__(256) void bn_relu_bwd_apply_kernel(const T* __restrict__ dz, const T* __restrict__ y,
-                                                                const float* __restrict__ scale, const float* __restrict__ shift,
-                                                                const float* __restrict__ mean, const float* __restrict__ rstd,
-                                                                const float* __restrict__ coef, T* __restrict__ dy, const HaloIdx h) {
-    constexpr int EPC = Vec16<T>::N, U = FVA_BN_UNROLL;
-    const int row_chunks = h.Wp * h.cpp;
-    const int cmask = h.cpp - 1, cshift = 31 - __builtin_clz(h.cpp);
-    const int cc = threadIdx.x & cmask;
-    const int row = blockIdx.x, b = row / h.Hp, yy = row - b * h.Hp - h.pad;
-    T* orow = dy + (int64_t)row * row_chunks * EPC;
-    if (yy < 0 || yy >= h.H) {
-        Vec16<T> zero;
-#pragma unroll
-        for (int e = 0; e < EPC; ++e) zero.set(e, 0.f);
-        for (int i = threadIdx.x; i < row_chunks; i += 256) *(Vec16<T>*)(orow + (int64_t)i * EPC) = zero;
-        return;
-    }
-    const int64_t m0 = ((int64_t)b * h.H + yy) * h.W;
-    // fp32 tensors: the three-term sum is formed in double and rounded ONCE (k1 = cb * rstd and k2 = cc - k1 * mean rounded to fp32 first
-    // would each leave 2^-24 of a term that may be larger than the result; v_fma_f64 runs at half the fp32 rate on this chip and the pass
-    // is HBM-bound).  bf16 tensors: fp32 arithmetic, the store's 2^-9 is the error.
-    using K = typename std::conditional<std::is_same<T, float>::value, double, float>::type;
-    float sc[EPC], sh[EPC];
-    K ka[EPC], k1[EPC], k2[EPC];
-#pragma unroll
-    for (int e = 0; e < EPC; ++e) {
-        const int c = cc * EPC + e;
-        sc[e] = scale[c]; sh[e] = shift[c];
-        if constexpr (std::is_same<T, float>::value) {
-            ka[e] = (double)coef[c];
-            k1[e] = (double)coef[h.C + c] * (double)rstd[c];
-            k2[e] = (double)coef[2 * h.C + c] - k1[e] * (double)mean[c];
-        } else {
-            const BnBwdK k = bn_bwd_pack_coef(coef[c], shift[c], mean[c], rstd[c], coef[h.C + c], coef[2 * h.C + c]);
-            ka[e] = k.a; k1[e] = k.k1; k2[e] = k.k2;
-        }
-    }
-    for (int i0 = threadIdx.x; i0 < row_chunks; i0 += 256 * U) {
-        Vec16<T> g[U], v[U];
-        bool ok[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int i = i0 + u * 256;
-            const int xx = (i >> cshift) - h.pad;
-            ok[u] = i < row_chunks && xx >= 0 && xx < h.W;
-            const int64_t off = (m0 + (ok[u] ? xx : 0)) * h.C + cc * EPC;
-            g[u] = ld_last<T>(dz + off);
-            v[u] = ld_last<T>(y + off);
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int i = i0 + u * 256;
-            Vec16<T> out;
-#pragma unroll
-            for (int e = 0; e < EPC; ++e) {
-                const float yv = v[u].get(e);
-                const float du = __builtin_fmaf(yv, sc[e], sh[e]) > 0.f ? g[u].get(e) : 0.f;
-                const K r = ka[e] * (K)du + (k1[e] * (K)yv + k2[e]);
-                out.set(e, ok[u] ? (float)r : 0.f);
-            }
-            if (i < row_chunks) *(Vec16<T>*)(orow + (int64_t)i * EPC) = out;
-        }
-    }
-}
 
 // The convolution bias in front of BatchNorm (vgg.py:43 builds Conv2d(bias=True)): training subtracts it again with the batch mean, so
 // the convolution runs without it; what it leaves is the running mean (it tracks mean(y) + b: running_mean += momentum * b after
@@ -1114,74 +1015,9 @@ __global__ void bn_eval_coeffs_bias_kernel(int C, const float* gamma, const floa
     }
 }
 
-int relu_halo(const char* who, int dtype, int B, int H, int W, int C, int pad, HaloIdx& h) {
-    int rc = check_chan(dtype, C, who);
-    if (rc) return rc;
-    if (B <= 0 || H <= 0 || W <= 0 || pad < 0 || pad > 1) return fva_fail(FVA_ERR_ARG, "%s: bad shape B=%d H=%d W=%d pad=%d", who, B, H, W, pad);
-    h = make_halo(B, H, W, C, pad, dtype == FVA_BF16 ? 8 : 4);
-    if (h.total >= (1ll << 31)) return fva_fail(FVA_ERR_ARG, "%s: tensor too large", who);
-    if ((h.cpp & (h.cpp - 1)) || h.cpp > 256) return fva_fail(FVA_ERR_ARG, "%s: C=%d must be a power of two (<= 256 chunks)", who, C);
-    return FVA_OK;
-}
-
 }  // namespace
 
 extern "C" {
-
-int fva_bn_relu_apply(int dtype, const void* y, const float* scale, const float* shift, void* z, int z_pad, int B, int H, int W, int C,
-                      void* stream) {
-    HaloIdx h;
-    const int rc = relu_halo("fva_bn_relu_apply", dtype, B, H, W, C, z_pad, h);
-    if (rc) return rc;
-    if (!y || !scale || !shift || !z) return fva_fail(FVA_ERR_ARG, "fva_bn_relu_apply: null pointer");
-    hipStream_t s = (hipStream_t)stream;
-    if (dtype == FVA_BF16)
-        hipLaunchKernelGGL(bn_relu_apply_kernel<bf16_t>, dim3(B * h.Hp), dim3(256), 0, s, (const bf16_t*)y, scale, shift, (bf16_t*)z, h);
-    else
-        hipLaunchKernelGGL(bn_relu_apply_kernel<float>, dim3(B * h.Hp), dim3(256), 0, s, (const float*)y, scale, shift, (float*)z, h);
-    FVA_LAUNCH_CHECK("bn_relu_apply_kernel");
-    return FVA_OK;
-}
-
-int fva_bn_relu_bwd_reduce(int dtype, const void* dz, const void* y, const float* scale, const float* shift, const float* save_mean,
-                           const float* save_rstd, float* partial, int32_t nblocks, int64_t M, int C, void* stream) {
-    const char* who = "fva_bn_relu_bwd_reduce";
-    const int rc = check_chan(dtype, C, who);
-    if (rc) return rc;
-    const int epc = dtype == FVA_BF16 ? 8 : 4;
-    const int cpp = C / epc;
-    if (cpp > 256 || 256 % cpp) return fva_fail(FVA_ERR_ARG, "%s: C=%d unsupported", who, C);
-    if (!dz || !y || !scale || !shift || !save_mean || !save_rstd || !partial || M <= 0) return fva_fail(FVA_ERR_ARG, "%s: bad argument", who);
-    const int rows = bwd_rows_per_block(M, C, epc);
-    if (nblocks != cdiv(M, rows)) return fva_fail(FVA_ERR_ARG, "%s: nblocks %d != fva_bn_bwd_blocks() = %d", who, nblocks, cdiv(M, rows));
-    const int smem = 2 * (256 / cpp) * C * 4;
-    hipStream_t s = (hipStream_t)stream;
-    if (dtype == FVA_BF16)
-        hipLaunchKernelGGL(bn_relu_bwd_reduce_kernel<bf16_t>, dim3(nblocks), dim3(256), smem, s, (const bf16_t*)dz, (const bf16_t*)y, scale, shift,
-                           save_mean, save_rstd, partial, M, C, rows);
-    else
-        hipLaunchKernelGGL(bn_relu_bwd_reduce_kernel<float>, dim3(nblocks), dim3(256), smem, s, (const float*)dz, (const float*)y, scale, shift,
-                           save_mean, save_rstd, partial, M, C, rows);
-    FVA_LAUNCH_CHECK("bn_relu_bwd_reduce_kernel");
-    return FVA_OK;
-}
-
-int fva_bn_relu_bwd_apply(int dtype, const void* dz, const void* y, const float* scale, const float* shift, const float* save_mean,
-                          const float* save_rstd, const float* coef, void* dy, int dy_pad, int B, int H, int W, int C, void* stream) {
-    HaloIdx h;
-    const int rc = relu_halo("fva_bn_relu_bwd_apply", dtype, B, H, W, C, dy_pad, h);
-    if (rc) return rc;
-    if (!dz || !y || !scale || !shift || !save_mean || !save_rstd || !coef || !dy) return fva_fail(FVA_ERR_ARG, "fva_bn_relu_bwd_apply: null pointer");
-    hipStream_t s = (hipStream_t)stream;
-    if (dtype == FVA_BF16)
-        hipLaunchKernelGGL(bn_relu_bwd_apply_kernel<bf16_t>, dim3(B * h.Hp), dim3(256), 0, s, (const bf16_t*)dz, (const bf16_t*)y, scale, shift,
-                           save_mean, save_rstd, coef, (bf16_t*)dy, h);
-    else
-        hipLaunchKernelGGL(bn_relu_bwd_apply_kernel<float>, dim3(B * h.Hp), dim3(256), 0, s, (const float*)dz, (const float*)y, scale, shift,
-                           save_mean, save_rstd, coef, (float*)dy, h);
-    FVA_LAUNCH_CHECK("bn_relu_bwd_apply_kernel");
-    return FVA_OK;
-}
 
 int fva_bn_bias_running_mean(int32_t C, float* running_mean, const float* bias, float momentum, void* stream) {
     if (!running_mean || !bias || C <= 0) return fva_fail(FVA_ERR_ARG, "fva_bn_bias_running_mean: bad argument");

@@ -277,6 +277,21 @@ def _dgrad(d, dy, wd, dx, addend_ptr, src, dtype):
     _lib.call('fva_conv_dgrad', C.byref(d), _p(dy), _p(wd), _p(dx), C.c_void_p(addend_ptr or 0), _stream())
 
 
+def _wgrad_dgrad(d, x_ptr, dy, wd, wshape, hold, weight, need_dx, addend_ptr=None, src=None):
+    """The tail of a convolution block's backward pass, given dy (halo NHWC): dW by fva_conv_wgrad on wgrad_stream(), then, if asked for,
+    dx by _dgrad (``addend_ptr`` / ``src``: its fusion arguments; the VGG blocks have none).  ``hold``: what the side stream must keep
+    alive besides dy and the workspace (the saved input).  Returns (dx_buf or None, dw)."""
+    dw = torch.empty(wshape, dtype=torch.float32, device=dy.device)
+    ws_bytes = _lib.load().fva_conv_wgrad_workspace(C.byref(d))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dy.device)
+    _lib.call('fva_conv_wgrad', C.byref(d), C.c_void_p(x_ptr), _p(dy), _p(dw), 0, _p(ws), ws_bytes, wgrad_stream(hold + (dy, ws), weight))     # NOT dw: a second reference makes AccumulateGrad clone it (on the main stream)
+    dx = None
+    if need_dx:
+        dx = torch.empty((d.B, d.H, d.W, d.Cin), dtype=dy.dtype, device=dy.device)
+        _dgrad(d, dy, wd, dx, addend_ptr, src, dy.dtype)
+    return dx, dw
+
+
 # ---- the forward apply pass of a block, deferred into the 1x1 convolution that consumes it -------------------------------------------
 # z = SiLU(BN(y)) (+ identity) of a block is an HBM round trip of its own (read y [+ identity], write z), and the residual blocks' conv1
 # (1x1) then reads z straight back.  Inside ``defer_apply_scope()`` -- Darknet.forward opens one per stage, around its own modules only --
@@ -741,14 +756,7 @@ def conv_block_bwd(s, dz_ptr, need_dx, addend_ptr=None):
         _lib.call('fva_bn_silu_bwd_apply', code, C.c_void_p(dz_ptr), _p(s.y), _p(s.scale), _p(s.shift), _p(s.mean), _p(s.rstd),
                   _p(coef), _p(dy), 1, d.B, s.OH, s.OW, Cout, _stream())
     del fused
-    dw = torch.empty(s.wshape, dtype=torch.float32, device=dev)
-    ws_bytes = lib.fva_conv_wgrad_workspace(C.byref(d))
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    _lib.call('fva_conv_wgrad', C.byref(d), C.c_void_p(s.x_ptr), _p(dy), _p(dw), 0, _p(ws), ws_bytes, wgrad_stream((s.x, getattr(s, 'keep', None), dy, ws), s.weight))     # NOT dw: a second reference makes AccumulateGrad clone it (on the main stream)
-    dx = None
-    if need_dx:
-        dx = torch.empty((d.B, d.H, d.W, d.Cin), dtype=dtype, device=dev)
-        _dgrad(d, dy, s.wd, dx, addend_ptr, s.x_src, dtype)
+    dx, dw = _wgrad_dgrad(d, s.x_ptr, dy, s.wd, s.wshape, (s.x, getattr(s, 'keep', None)), s.weight, need_dx, addend_ptr, s.x_src)
     # this block's saved state is spent: drop what it references (its output tensor may outlive the step in the caller's hands and
     # still points here through _fva_prod; the side stream's launches keep their own references until the join)
     s.__dict__.clear()

@@ -19,8 +19,8 @@ import torch.nn.functional as F
 
 from . import _lib
 from .fc_ops import rows_as
-from .ops import (_BNState, _code, _grad_like, _p, _stream, dense_view, flush_pending_apply, get_compute_dtype, halo_alloc, halo_info, packed_weights,
-                  require_gpu, to_dense, to_halo, wgrad_stream)
+from .ops import (_BNState, _code, _grad_like, _p, _stream, _wgrad_dgrad, dense_view, flush_pending_apply, get_compute_dtype, halo_alloc, halo_info,
+                  packed_weights, require_gpu, to_dense, to_halo)
 
 __all__ = ['conv_bias_relu', 'max_pool2', 'conv_bn_relu', 'adaptive_avg_pool7_flatten']
 
@@ -57,15 +57,8 @@ class ConvBiasReLUFn(torch.autograd.Function):
         srows = lib.fva_colsum_scratch_rows(rows)
         scratch = torch.empty((srows, Cout), dtype=torch.float32, device=dev) if srows else None
         _lib.call('fva_colsum', _p(part), rows, Cout, _p(dbias), _p(scratch) if srows else None, _stream())
-        dw = torch.empty(wshape, dtype=torch.float32, device=dev)
-        wsb = lib.fva_conv_wgrad_workspace(C.byref(d))
-        ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-        _lib.call('fva_conv_wgrad', C.byref(d), C.c_void_p(x_ptr), _p(dy), _p(dw), 0, _p(ws), wsb, wgrad_stream((keep, dy, ws), ctx.weight))
-        dx = None
-        if ctx.needs_input_grad[0]:
-            dxb = torch.empty((B, H, W, d.Cin), dtype=dtype, device=dev)
-            _lib.call('fva_conv_dgrad', C.byref(d), _p(dy), _p(wd), _p(dxb), C.c_void_p(0), _stream())
-            dx = _grad_like(dxb, ctx.x_like)
+        dxb, dw = _wgrad_dgrad(d, x_ptr, dy, wd, wshape, (keep,), ctx.weight, ctx.needs_input_grad[0])
+        dx = _grad_like(dxb, ctx.x_like) if dxb is not None else None
         return dx, dw, dbias, None
 
 
@@ -95,17 +88,7 @@ def conv_bias_relu(x, conv, dtype=None):
     if conv.kernel_size != (3, 3) or conv.stride != (1, 1) or conv.padding != (1, 1) or conv.bias is None:
         raise RuntimeError('conv_bias_relu: only the VGG block (3x3, stride 1, padding 1, bias) is on this path')
     dtype = dtype or get_compute_dtype()
-    weight, cin = conv.weight, conv.weight.shape[1]
-    if cin % _CIN_ALIGN:                     # the RGB input of the first block: zero channels (and zero filter taps) up to 32
-        extra = _CIN_ALIGN - cin % _CIN_ALIGN
-        weight = F.pad(weight, (0, 0, 0, 0, 0, extra))
-        if x.requires_grad:
-            x = F.pad(x, (0, 0, 0, 0, 0, extra))
-        else:                                # an image batch: written straight into a zeroed halo buffer, no padded fp32 copy
-            B, _, H, W = x.shape
-            buf = torch.zeros((B, H + 2, W + 2, cin + extra), dtype=dtype, device=x.device)
-            buf[:, 1:-1, 1:-1, :cin] = x.permute(0, 2, 3, 1)
-            x = buf[:, 1:-1, 1:-1, :].permute(0, 3, 1, 2)
+    x, weight = _pad_rgb(x, conv.weight, dtype)
     return ConvBiasReLUFn.apply(x, weight, conv.bias, dtype)
 
 
@@ -115,7 +98,7 @@ def max_pool2(x, dtype=None):
 
 
 def _pad_rgb(x, weight, dtype):
-    """The RGB input of a first block: zero channels (and zero filter taps) up to 32 (as conv_bias_relu does it)."""
+    """The RGB input of a first block: zero channels (and zero filter taps) up to 32."""
     cin = weight.shape[1]
     if cin % _CIN_ALIGN == 0:
         return x, weight
@@ -193,15 +176,8 @@ class ConvBNReLUFn(torch.autograd.Function):
         dy = torch.empty((B, H + 2, W + 2, Cout), dtype=dtype, device=dev)
         _lib.call('fva_bn_relu_bwd_apply', code, C.c_void_p(dz_ptr), _p(y), _p(scale), _p(shift), _p(mean), _p(rstd), _p(coef), _p(dy), 1,
                   B, H, W, Cout, _stream())
-        dw = torch.empty(wshape, dtype=torch.float32, device=dev)
-        wsb = lib.fva_conv_wgrad_workspace(C.byref(d))
-        ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-        _lib.call('fva_conv_wgrad', C.byref(d), C.c_void_p(x_ptr), _p(dy), _p(dw), 0, _p(ws), wsb, wgrad_stream((keep, dy, ws), ctx.weight))
-        dx = None
-        if ctx.needs_input_grad[0]:
-            dxb = torch.empty((B, H, W, d.Cin), dtype=dtype, device=dev)
-            _lib.call('fva_conv_dgrad', C.byref(d), _p(dy), _p(wd), _p(dxb), C.c_void_p(0), _stream())
-            dx = _grad_like(dxb, ctx.x_like)
+        dxb, dw = _wgrad_dgrad(d, x_ptr, dy, wd, wshape, (keep,), ctx.weight, ctx.needs_input_grad[0])
+        dx = _grad_like(dxb, ctx.x_like) if dxb is not None else None
         dbias = torch.zeros(Cout, dtype=torch.float32, device=dev)
         ctx.saved = ctx.x_like = ctx.weight = None          # released by the backward pass that used them
         return dx, dw, dbias, dgamma, dbeta, None, None, None
