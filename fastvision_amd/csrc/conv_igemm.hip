@@ -73,7 +73,7 @@ struct IgemmParams {
     float *ax_save_mean, *ax_save_rstd, *ax_scale_out, *ax_shift_out;
     long long* stamps;   // diagnostic (fva_conv_debug_stamps): [stamp_rows][8] wall-clock stamps of the block's phases (igemm_kernel)
     int stamp_rows;
-    int pt_tx, pt_ty, pt_H, pt_W;   // pconv_kernel: tiles of 8 x 32 output pixels per image (x, y), output image size
+    int pt_tx, pt_ty, pt_H, pt_W;   // patch_kernel: output tiles per image (x, y; 8 x 32 or 8 x 64 pixels each), output image size
     int pt_tiles, pt_tpb;           //   tiles of the launch, consecutive tiles per block (the resident weights are staged once per block)
     FastDiv pt_div_tx, pt_div_img;  //   divisions by pt_tx and pt_tx * pt_ty
 };
@@ -940,46 +940,122 @@ int launch_one(const IgemmParams& p, hipStream_t s) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// Patch convolution: the thin 3x3 stride-1 layers (32 -> 64 at 320^2, 64 -> 128 at 160^2 and their data gradients, 64 -> 32 and
-// 128 -> 64: reduction channels C <= 128, outputs N <= 128, bf16).  The implicit-GEMM kernels above fetch every tap's A tile
-// separately: 9 x (256 pixels x 128 B) through L2 -> LDS for 256 output pixels, and with K this short nothing amortises it -- the
-// block-phase stamps (profiles/r02_tile_phases.md) put 43-75 % of a block's life into a k loop that runs at the L2 -> LDS rate
-// (17-20 TB/s chip-wide), four times slower than its MFMAs.  Here a block owns a PATCH of 8 x 32 output pixels of one image: the
-// (8+2) x (32+2) input pixels it needs are staged ONCE (LDS-DMA, pixel-major rows of one 64- or 32-channel slice, XOR-swizzled on
-// the source side), and the nine taps are nine shifted fragment reads of that image: 1.33 instead of 9 input bytes per output
-// pixel and channel.  The weights of one (tap, channel slice) are a [N][slice] matrix: all nine resident when they fit 36 KiB
-// (C x N <= 2048), else streamed through two LDS slots one step ahead of the MFMAs.  4 waves, each 2 patch rows (64 pixels =
-// four 16-pixel A tiles) x all N columns; epilogues, statistics and the store loop are the implicit-GEMM kernel's
-// (EPI_STATS / EPI_PLAIN / EPI_BNB, tile row r <-> patch pixel (r / 32, r % 32)).  Same products in the same order per output as
-// igemm_kernel with tap-major k order -- but slice-major there (ktaps), so results agree to fp32 summation order, not bit for bit.
-template <int CS, int BN, int NSL, int EPI>
-__global__ __launch_bounds__(256, 2) void pconv_kernel(const IgemmParams p) {
-    constexpr int TH = 8, TW = 32, PW = TW + 2, NPIX = (TH + 2) * PW;             // 340 patch pixels
-    constexpr int PIXB = CS * 2;                                                   // bytes of a pixel row in LDS: 128 / 64
-    constexpr int CPP = PIXB / 16;                                                 // 16-byte chunks per pixel: 8 / 4
-    constexpr int PPI = 1024 / PIXB;                                               // pixels per LDS-DMA instruction: 8 / 16
-    constexpr int PATCH_INSTR = (NPIX + PPI - 1) / PPI, PATCH_BYTES = PATCH_INSTR * 1024;
-    constexpr int WSTEP_BYTES = BN * PIXB, WPW = WSTEP_BYTES / 1024 / 4;           // one (tap, slice) matrix; its DMA instructions per wave
+// Patch kernel: the thin 3x3 bf16 layers (reduction channels C <= 128, outputs N <= 128).  The implicit-GEMM kernels above fetch
+// every tap's A tile separately: 9 x (256 pixels x 128 B) through L2 -> LDS for 256 output pixels, and with K this short nothing
+// amortises it -- the block-phase stamps (profiles/r02_tile_phases.md) put 43-75 % of a block's life into a k loop that runs at the
+// L2 -> LDS rate (17-20 TB/s chip-wide), four times slower than its MFMAs.  Here a block owns a PATCH: the input pixels that one
+// tile of output pixels needs are staged ONCE (LDS-DMA, pixel-major rows of one 64- or 32-channel slice, XOR-swizzled on the source
+// side), and the nine taps are nine shifted fragment reads of that image.  The weights of one (tap, channel slice) are a [N][slice]
+// matrix: all nine resident when they fit 36 KiB (C x N <= 2048), else streamed through two LDS slots one step ahead of the MFMAs.
+// 4 waves, each a share of the tile's rows x all N columns; epilogues, statistics and the store loop are the implicit-GEMM kernel's
+// (EPI_STATS / EPI_PLAIN / EPI_BNB, tile row r <-> output pixel (r / TW, r % TW) of the tile).
+// What differs between the two uses is the geometry G: patch and tile size, the patch pixel each A fragment of a wave starts at, the
+// pixel offset of a tap and the accumulator group a fragment feeds, the tile row of a group's lane, and the filter tap of a step.
+
+// Stride 1, forward and data gradient (32 -> 64 at 320^2, 64 -> 128 at 160^2; 64 -> 32, 128 -> 64 and 64 -> 64): 8 x 32 output pixels
+// from (8+2) x (32+2) input pixels, 1.33 instead of 9 input bytes per output pixel and channel.  Wave w owns patch rows 2w, 2w + 1
+// (64 pixels = four 16-pixel A tiles, one accumulator group each: fragment a = row (a >> 1), x half (a & 1)); tap (dy, dx) adds
+// dy * PW + dx.  Same products in the same order per output as igemm_kernel with tap-major k order -- but slice-major there (ktaps),
+// so results agree to fp32 summation order, not bit for bit.
+struct PconvGeom {
+    static constexpr int PH = 10, PW = 34, PW_RCP = 1928;     // patch rows x width; (pix * PW_RCP) >> 16 == pix / PW, exact below 400
+    static constexpr int OY = 8, OX = 32;                     // patch origin step per tile
+    static constexpr int TH = 8, TW_LOG2 = 5;                 // output tile: 8 x 32
+    static constexpr int NA = 4, NGRP = 4;                    // A fragments read per tap, accumulator groups per wave
+    static constexpr int MIN_CS = 32;
+    static constexpr bool STATS = true, BNB_LOOPS = true;
+    static constexpr const char *LABEL = "pconv", *KERNEL = "pconv_kernel";
+    static __device__ __forceinline__ int frag_pix(int w, int a, int r16) { return (2 * w + (a >> 1)) * PW + (a & 1) * 16 + r16; }
+    static __device__ __forceinline__ int tap_off(int t) { return (t / 3) * PW + (t % 3); }
+    static __device__ __forceinline__ int group(int, int a) { return a; }
+    static __device__ __forceinline__ int tile_row(int w, int grp, int r16) { return (2 * w + (grp >> 1)) * 32 + (grp & 1) * 16 + r16; }
+    static __device__ __forceinline__ int filter_tap(const IgemmParams& p, int tap) {   // patch tap -> filter tap: flipped for the data gradient
+        int tw = 0;
+#pragma unroll
+        for (int i = 0; i < 9; ++i)
+            if (i == tap) tw = p.tap_w[i];
+        return tw;
+    }
+    template <int EPI> static int launch_form(const IgemmParams& p, int tiles, hipStream_t s);   // the channel forms built for this geometry
+};
+
+// Stride-2 data gradient (64 -> 32 channels at 640^2, 128 -> 64 at 320^2).
+//   dx[2i + py][2j + px] = sum over the taps (kh, kw) with kh = 1 (py = 0) or kh in {0, 2} (py = 1), likewise kw / px, of
+//                          dy[i + (kh == 0)][j + (kw == 0)] . W[kh][kw]
+// Until round 3 these ran as two "paired" implicit-GEMM launches (both x parities as N' = 2 Cin columns: 4/3 of the MACs, every
+// tap's dy tile fetched again) -- 505 / 330 us for 1.26 / 1.05 GB of HBM traffic.  Here a block owns 4 x 32 cells = 8 x 64 dx
+// pixels: the (4+1) x (32+1) dy pixels they need are staged once (21 KiB per 64-channel slice), every tap is ONE shifted fragment
+// read feeding exactly the parity class it belongs to (the exact 9/4 MACs per dx pixel), wave w owns cell row w with eight
+// accumulator groups (4 parity classes py * 2 + px  x  2 halves of the row).  Accumulator element (class (py, px), half xt, j) =
+// dx pixel (2 w + py, 2 (16 xt + 4 g + j) + px) of the tile.  Weights: the plain [9][Cin][Cout] dgrad layout.
+struct Pdgrad2Geom {
+    static constexpr int PH = 5, PW = 33, PW_RCP = 1986;
+    static constexpr int OY = 4, OX = 32;
+    static constexpr int TH = 8, TW_LOG2 = 6;                 // output tile: 8 x 64
+    static constexpr int NA = 2, NGRP = 8;
+    static constexpr int MIN_CS = 64;
+    // no EPI_STATS form is built; the fused-statistics epilogue inside the tile loop spills (35 registers): one tile per block there
+    static constexpr bool STATS = false, BNB_LOOPS = false;
+    static constexpr const char *LABEL = "pdgrad2", *KERNEL = "pdgrad2_kernel";
+    static __device__ __forceinline__ int frag_pix(int w, int a, int r16) { return w * PW + a * 16 + r16; }
+    static __device__ __forceinline__ int tap_off(int t) { return (t / 3 == 0 ? PW : 0) + (t % 3 == 0 ? 1 : 0); }
+    static __device__ __forceinline__ int group(int t, int a) { return ((t / 3 == 1 ? 0 : 2) + (t % 3 == 1 ? 0 : 1)) * 2 + a; }
+    static __device__ __forceinline__ int tile_row(int w, int grp, int r16) {
+        const int c = grp >> 1, xt = grp & 1;
+        return w * 128 + 2 * r16 + ((c >> 1) * 64 + xt * 32 + (c & 1));   // the group's part apart: a constant offset once unrolled
+    }
+    static __device__ __forceinline__ int filter_tap(const IgemmParams&, int tap) { return tap; }   // tap = kh * 3 + kw
+    template <int EPI> static int launch_form(const IgemmParams& p, int tiles, hipStream_t s);
+};
+
+// The LDS layout of patch_kernel<G, CS, BN, NSL, EPI>, for the kernel's offsets and the launcher's dynamic LDS size alike:
+// [patch | weights] during the k loop, the epilogue's bf16 tile from 0, the EPI_BNB coefficient table behind both.
+template <typename G, int CS, int BN, int NSL, int EPI>
+struct PatchLayout {
+    static_assert((CS == 32 || CS == 64) && CS >= G::MIN_CS, "64-channel slices (128-byte pixel rows), or 32 where the geometry has them");
+    static_assert(EPI != EPI_STATS || G::STATS, "this geometry has no statistics epilogue");
+    static constexpr int NPIX = G::PH * G::PW;                                     // patch pixels: 340 / 165
+    static constexpr int PIXB = CS * 2;                                            // bytes of a pixel row in LDS: 128 / 64
+    static constexpr int CPP = PIXB / 16;                                          // 16-byte chunks per pixel: 8 / 4
+    static constexpr int PPI = 1024 / PIXB;                                        // pixels per LDS-DMA instruction: 8 / 16
+    static constexpr int PATCH_INSTR = (NPIX + PPI - 1) / PPI, PATCH_BYTES = PATCH_INSTR * 1024;
+    static constexpr int WSTEP_BYTES = BN * PIXB;                                  // one (tap, slice) matrix
     static_assert(WSTEP_BYTES % 4096 == 0, "whole DMA instructions per wave");
-    constexpr int STEPS = 9 * NSL;
-    constexpr bool RESIDENT = NSL == 1 && 9 * WSTEP_BYTES <= 36 * 1024;
-    constexpr int WBUF_BYTES = (RESIDENT ? 9 : 2) * WSTEP_BYTES;
-    constexpr int BM = 256, NT = 256, NTILE = BN / 16, KS = CS / 32;
-    constexpr int PITCH = BN * 2 + 16, TILE_BYTES = BM * PITCH;
+    static constexpr bool RESIDENT = NSL == 1 && 9 * WSTEP_BYTES <= 36 * 1024;
+    static constexpr int WBUF_BYTES = (RESIDENT ? 9 : 2) * WSTEP_BYTES;
+    // only the resident-weight forms loop over tiles (a ring re-streams its weights per tile anyway, and inside a loop its per-step
+    // staging addresses are hoisted as loop invariants: 120-240 spilled registers)
+    static constexpr bool LOOPED = RESIDENT && (EPI != EPI_BNB || G::BNB_LOOPS);
+    static constexpr int BM = G::TH << G::TW_LOG2, PITCH = BN * 2 + 16, TILE_BYTES = BM * PITCH;
     // resident weights live across the block's tiles: the epilogue's tile may alias the patch, not them; a ring is re-streamed per tile
-    constexpr int WOFF = RESIDENT && TILE_BYTES > PATCH_BYTES ? TILE_BYTES : PATCH_BYTES;
-    constexpr int COEF0 = TILE_BYTES > WOFF + WBUF_BYTES ? TILE_BYTES : WOFF + WBUF_BYTES;   // BNB coefficient table: clear of both uses
+    static constexpr int WOFF = RESIDENT && TILE_BYTES > PATCH_BYTES ? TILE_BYTES : PATCH_BYTES;
+    static constexpr int COEF0 = TILE_BYTES > WOFF + WBUF_BYTES ? TILE_BYTES : WOFF + WBUF_BYTES;   // BNB coefficient table: clear of both uses
+    static constexpr int SMEM = COEF0 + (EPI == EPI_BNB ? 4 * BN * 4 : 0);
+    static_assert(SMEM <= 80 * 1024, "two blocks per CU");
+    static constexpr int STATS_RP = BN + 4;                                        // EPI_STATS scratch [2][4 waves][16][STATS_RP] floats from 0
+    static_assert(EPI != EPI_STATS || 2 * 4 * 16 * STATS_RP * 4 <= TILE_BYTES, "the statistics scratch stays inside the epilogue tile's bytes");
+};
+
+template <typename G, int CS, int BN, int NSL, int EPI>
+__global__ __launch_bounds__(256, 2) void patch_kernel(const IgemmParams p) {
+    using L = PatchLayout<G, CS, BN, NSL, EPI>;
+    constexpr int PW = G::PW, NPIX = L::NPIX, PIXB = L::PIXB, CPP = L::CPP, PPI = L::PPI, PATCH_INSTR = L::PATCH_INSTR;
+    constexpr int WSTEP_BYTES = L::WSTEP_BYTES, WPW = WSTEP_BYTES / 1024 / 4;      // a weight matrix's DMA instructions per wave
+    constexpr int STEPS = 9 * NSL;
+    constexpr bool RESIDENT = L::RESIDENT, LOOPED = L::LOOPED;
+    constexpr int TH = G::TH, TWL = G::TW_LOG2, TW = 1 << TWL;
+    constexpr int BM = L::BM, NT = 256, NTILE = BN / 16, KS = CS / 32, PITCH = L::PITCH;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* const patch = smem;
-    char* const wbuf = smem + WOFF;
+    char* const wbuf = smem + L::WOFF;
 
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int r16 = lane & 15, g = lane >> 4;
     const int nwg = gridDim.x, bid = blockIdx.x;
     const int xcd = bid & 7, xq = nwg >> 3, xr = nwg & 7;
-    const int tile0 = ((xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + (bid >> 3)) * (RESIDENT ? p.pt_tpb : 1);
+    const int tile0 = ((xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + (bid >> 3)) * (LOOPED ? p.pt_tpb : 1);
     const int Hp = p.in_img / p.in_row, Wp = p.in_row;
-    float* coef_tab = (float*)(smem + COEF0);
+    float* coef_tab = (float*)(smem + L::COEF0);
     if constexpr (EPI == EPI_BNB) bnb_fill_lds<BN, NT>(p, coef_tab, tid, 0);   // before the first LDS-DMA; read in the epilogue
     int b = 0, ty = 0, tx = 0, yorg = 0, xorg = 0;                     // the current tile (set at the top of the tile loop)
 
@@ -993,7 +1069,7 @@ __global__ __launch_bounds__(256, 2) void pconv_kernel(const IgemmParams p) {
             if (j < PATCH_INSTR) {
                 int pix = j * PPI + lane / CPP;
                 pix = pix < NPIX ? pix : NPIX - 1;
-                const int py = (pix * 1928) >> 16, px = pix - py * PW;             // / 34, exact below 400
+                const int py = (pix * G::PW_RCP) >> 16, px = pix - py * PW;        // / PW
                 int iy = yorg + py, ix = xorg + px;
                 iy = iy < Hp ? iy : Hp - 1;                                        // tiles that overhang the image: rows / columns that are
                 ix = ix < Wp ? ix : Wp - 1;                                        // never stored read a valid pixel
@@ -1004,11 +1080,7 @@ __global__ __launch_bounds__(256, 2) void pconv_kernel(const IgemmParams p) {
     };
     auto stage_w = [&](int step, char* dst) {                          // step = slice * 9 + tap
         const int slice = step / 9, tap = step - slice * 9;
-        int tw = 0;
-#pragma unroll
-        for (int i = 0; i < 9; ++i)
-            if (i == tap) tw = p.tap_w[i];
-        const bf16_t* src0 = (const bf16_t*)p.wt + (int64_t)tw * p.N * p.C + slice * CS;
+        const bf16_t* src0 = (const bf16_t*)p.wt + (int64_t)G::filter_tap(p, tap) * p.N * p.C + slice * CS;
 #pragma unroll
         for (int i = 0; i < WPW; ++i) {
             const int j = i * 4 + w;
@@ -1019,20 +1091,19 @@ __global__ __launch_bounds__(256, 2) void pconv_kernel(const IgemmParams p) {
         }
     };
 
-    f32x4 acc[4][NTILE];
-    // this lane's A rows: wave w owns patch rows 2w, 2w + 1; tile mt = row (mt >> 1), x half (mt & 1); tap (dy, dx) adds dy * PW + dx
-    int pix0[4];
+    f32x4 acc[G::NGRP][NTILE];
+    int pix0[G::NA];   // this lane's first patch pixel per A fragment; a tap adds G::tap_off
     int opq = 0;   // re-made opaque in every tile: the 72 + fragment addresses of a tile are then computed where they are used, not
                    // hoisted out of the tile loop (as loop invariants they cost 150-280 spilled registers)
     auto compute = [&](int tap, const char* wb) {
-        const int tapoff = (tap / 3) * PW + (tap % 3);
+        const int tapoff = G::tap_off(tap);
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
-            bf16x8 af[4], bfr[NTILE];
+            bf16x8 af[G::NA], bfr[NTILE];
 #pragma unroll
-            for (int mt = 0; mt < 4; ++mt) {
-                const int pix = pix0[mt] + tapoff;
-                af[mt] = *(const bf16x8*)(patch + pix * PIXB + (((ks * 4 + g) ^ swz(pix)) << 4));
+            for (int a = 0; a < G::NA; ++a) {
+                const int pix = pix0[a] + tapoff;
+                af[a] = *(const bf16x8*)(patch + pix * PIXB + (((ks * 4 + g) ^ swz(pix)) << 4));
             }
 #pragma unroll
             for (int nt = 0; nt < NTILE; ++nt) {
@@ -1040,9 +1111,10 @@ __global__ __launch_bounds__(256, 2) void pconv_kernel(const IgemmParams p) {
                 bfr[nt] = *(const bf16x8*)(wb + n * PIXB + (((ks * 4 + g) ^ swz(n)) << 4));
             }
 #pragma unroll
-            for (int mt = 0; mt < 4; ++mt)
+            for (int a = 0; a < G::NA; ++a)
 #pragma unroll
-                for (int nt = 0; nt < NTILE; ++nt) acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[nt], af[mt], acc[mt][nt], 0, 0, 0);   // swapped: foreach_acc
+                for (int nt = 0; nt < NTILE; ++nt)
+                    acc[G::group(tap, a)][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[nt], af[a], acc[G::group(tap, a)][nt], 0, 0, 0);   // swapped: foreach_acc
         }
     };
 
@@ -1050,10 +1122,8 @@ __global__ __launch_bounds__(256, 2) void pconv_kernel(const IgemmParams p) {
 #pragma unroll
         for (int t = 0; t < 9; ++t) stage_w(t, wbuf + t * WSTEP_BYTES);
     }
-    // only the resident-weight forms loop over tiles (a ring re-streams its weights per tile anyway, and inside a loop its per-step
-    // staging addresses are hoisted as loop invariants: 120-240 spilled registers)
 #pragma unroll 1
-    for (int it = 0; it < (RESIDENT ? p.pt_tpb : 1); ++it) {
+    for (int it = 0; it < (LOOPED ? p.pt_tpb : 1); ++it) {
     const int tile = tile0 + it;
     if (tile >= p.pt_tiles) break;                                     // block-uniform
     b = (int)fd_div((uint32_t)tile, p.pt_div_img);
@@ -1062,13 +1132,13 @@ __global__ __launch_bounds__(256, 2) void pconv_kernel(const IgemmParams p) {
         ty = (int)fd_div((uint32_t)trem, p.pt_div_tx);
         tx = trem - ty * p.pt_tx;
     }
-    yorg = p.y0 + ty * TH;                                             // patch origin in the padded input
-    xorg = p.x0 + tx * TW;
+    yorg = p.y0 + ty * G::OY;                                          // patch origin in the padded input
+    xorg = p.x0 + tx * G::OX;
     asm volatile("" : "+v"(opq));
 #pragma unroll
-    for (int mt = 0; mt < 4; ++mt) pix0[mt] = (2 * w + (mt >> 1)) * PW + (mt & 1) * 16 + r16 + opq;
+    for (int a = 0; a < G::NA; ++a) pix0[a] = G::frag_pix(w, a, r16) + opq;
 #pragma unroll
-    for (int i = 0; i < 4; ++i)
+    for (int i = 0; i < G::NGRP; ++i)
 #pragma unroll
         for (int j = 0; j < NTILE; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
     if constexpr (RESIDENT) {
@@ -1103,29 +1173,28 @@ __global__ __launch_bounds__(256, 2) void pconv_kernel(const IgemmParams p) {
     }
     __syncthreads();   // LDS is free for the epilogue
 
-    // accumulator tile (mt, nt) of lane (r16, g) (MFMA operands swapped, see foreach_acc): tile row = patch pixel
-    // (2w + (mt >> 1), (mt & 1) * 16 + r16), columns nt * 16 + 4 g .. + 3
+    // accumulator group grp, n tile nt of lane (r16, g) (MFMA operands swapped, see foreach_acc): tile row G::tile_row(w, grp, r16),
+    // columns nt * 16 + 4 g .. + 3
     const bool full = (ty + 1) * TH <= p.pt_H && (tx + 1) * TW <= p.pt_W;
-    auto row_ok = [&](int rr) { return ty * TH + (rr >> 5) < p.pt_H && tx * TW + (rr & 31) < p.pt_W; };
+    auto rows_ok = [&](int grp) { const int rr = G::tile_row(w, grp, r16); return ty * TH + (rr >> TWL) < p.pt_H && tx * TW + (rr & (TW - 1)) < p.pt_W; };
     if constexpr (EPI == EPI_STATS) {
         if (p.stats != nullptr || p.stats_acc != nullptr) {
             f32x4 s1[NTILE], s2[NTILE];
 #pragma unroll
             for (int i = 0; i < NTILE; ++i) s1[i] = s2[i] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-            for (int mt = 0; mt < 4; ++mt) {
-                const bool ok = full || row_ok((2 * w + (mt >> 1)) * 32 + (mt & 1) * 16 + r16);
+            for (int grp = 0; grp < G::NGRP; ++grp) {
+                const bool ok = full || rows_ok(grp);
 #pragma unroll
                 for (int nt = 0; nt < NTILE; ++nt) {
-                    const f32x4 v = ok ? acc[mt][nt] : f32x4{0.f, 0.f, 0.f, 0.f};
+                    const f32x4 v = ok ? acc[grp][nt] : f32x4{0.f, 0.f, 0.f, 0.f};
                     s1[nt] += v;
                     s2[nt] += v * v;
                 }
             }
             // the 16 lane rows and the four waves through LDS, added by the column's thread in a fixed order (igemm_kernel's scheme)
             float* red = (float*)smem;  // [2][4 waves][16][RP]: below the tile's end, clear of resident weights
-            constexpr int RP = BN + 4;
-            static_assert(2 * 4 * 16 * RP * 4 <= TILE_BYTES, "the statistics scratch stays inside the epilogue tile's bytes");
+            constexpr int RP = L::STATS_RP;
 #pragma unroll
             for (int nt = 0; nt < NTILE; ++nt) {
                 *(f32x4*)(red + ((0 * 4 + w) * 16 + r16) * RP + nt * 16 + 4 * g) = s1[nt];
@@ -1146,22 +1215,22 @@ __global__ __launch_bounds__(256, 2) void pconv_kernel(const IgemmParams p) {
         }
     }
 #pragma unroll
-    for (int mt = 0; mt < 4; ++mt)
+    for (int grp = 0; grp < G::NGRP; ++grp)
 #pragma unroll
         for (int nt = 0; nt < NTILE; ++nt) {
-            const f32x4 v = acc[mt][nt];
-            *(u32x2*)(smem + ((2 * w + (mt >> 1)) * 32 + (mt & 1) * 16 + r16) * PITCH + (nt * 16 + 4 * g) * 2) = u32x2{cvt_pk_bf16(v[0], v[1]), cvt_pk_bf16(v[2], v[3])};
+            const f32x4 v = acc[grp][nt];
+            *(u32x2*)(smem + G::tile_row(w, grp, r16) * PITCH + (nt * 16 + 4 * g) * 2) = u32x2{cvt_pk_bf16(v[0], v[1]), cvt_pk_bf16(v[2], v[3])};
         }
     __syncthreads();
     store_tile_bf16<EPI, BM, BN, NT, PITCH>(p, smem, tid, 0, tile, [&](int rr) -> int64_t {
-        const int oy = ty * TH + (rr >> 5), ox = tx * TW + (rr & 31);
+        const int oy = ty * TH + (rr >> TWL), ox = tx * TW + (rr & (TW - 1));
         return oy < p.pt_H && ox < p.pt_W ? ((int64_t)b * p.pt_H + oy) * p.pt_W + ox : (int64_t)-1;
     }, nullptr, nullptr, EPI == EPI_BNB ? coef_tab : nullptr);
     __syncthreads();   // the next tile's patch lands where this tile's epilogue read
     }
 }
 
-// Layers the patch kernel serves (bf16, 3x3, stride 1): reduction channels C in {32, 64, 128}, outputs N in {32, 64, 128}, at most
+// Layers the patch kernel serves at stride 1 (bf16, 3x3): reduction channels C in {32, 64, 128}, outputs N in {32, 64, 128}, at most
 // C x N = 8192, on maps of at least 64 x 64 (below that the 8 x 32 patches overhang too much).  FVA_PCONV=0 switches it off.
 int g_pconv = -1;   // -1: read FVA_PCONV on first use; fva_conv_patch_kernel() sets it
 inline bool pconv_enabled() {
@@ -1175,270 +1244,63 @@ inline bool use_pconv(int dtype, int ksize, int stride, int C, int N, int H, int
     if (!pconv_enabled() || dtype != FVA_BF16 || ksize != 3 || stride != 1 || H < 64 || W < 64) return false;
     return (C == 32 && N == 64) || (C == 64 && N == 128) || (C == 64 && N == 32) || (C == 128 && N == 64) || (C == 64 && N == 64);
 }
-inline int pconv_tiles(int B, int H, int W) { return B * cdiv(H, 8) * cdiv(W, 32); }
+// stride-2 3x3 bf16 data gradients the patch kernel serves: reduction over C = Cout channels, N = Cin outputs.  Decided by the
+// channel counts alone (the weight packer must know the layout without seeing a feature-map size: these layers take the plain
+// [9][Cin][Cout] dgrad weights, the other thin stride-2 layers the paired layout).
+inline bool use_pdgrad2(int dtype, int ksize, int stride, int C, int N) {
+    return dtype == FVA_BF16 && ksize == 3 && stride == 2 && ((C == 64 && N == 32) || (C == 128 && N == 64));
+}
+template <typename G>
+inline int patch_tiles(int B, int H, int W) { return B * cdiv(H, G::TH) * cdiv(W, 1 << G::TW_LOG2); }   // H, W: the output image
 
-template <int CS, int BN, int NSL, int EPI>
-int launch_pconv_one(const IgemmParams& p0, int tiles, hipStream_t s) {
-    constexpr int PIXB = CS * 2, PPI = 1024 / PIXB, PATCH_BYTES = ((340 + PPI - 1) / PPI) * 1024, WSTEP = BN * PIXB;
-    constexpr bool RESIDENT = NSL == 1 && 9 * WSTEP <= 36 * 1024;
-    constexpr int WBUF = (RESIDENT ? 9 : 2) * WSTEP, TILE = 256 * (BN * 2 + 16);
-    constexpr int WOFF = RESIDENT && TILE > PATCH_BYTES ? TILE : PATCH_BYTES;
-    constexpr int smem = (TILE > WOFF + WBUF ? TILE : WOFF + WBUF) + (EPI == EPI_BNB ? 4 * BN * 4 : 0);
-    static_assert(smem <= 80 * 1024, "two blocks per CU");
-    // consecutive tiles per block: resident weights (36 KiB) cost more L2 -> LDS bytes than the patch itself when re-staged per tile
-    static const int tpb_env = [] { const char* e = getenv("FVA_PCONV_TPB"); return e ? atoi(e) : 0; }();
+template <typename G, int CS, int BN, int NSL, int EPI>
+int launch_patch_one(const IgemmParams& p0, int tiles, hipStream_t s) {
+    using L = PatchLayout<G, CS, BN, NSL, EPI>;
     IgemmParams p = p0;
     p.pt_tiles = tiles;
-    p.pt_tpb = RESIDENT ? (tpb_env > 0 ? tpb_env : 2) : 1;     // measured 1 / 2 / 4 / 8 on 32 -> 64 at 320^2: fwd 253 / 235 / 260 / 261 us, dgrad 218 / 209 / 214 / 224
-    const int blocks = cdiv(tiles, p.pt_tpb);
+    // consecutive tiles per block: resident weights (36 KiB) cost more L2 -> LDS bytes than the patch itself when re-staged per tile
+    p.pt_tpb = L::LOOPED ? 2 : 1;     // measured 1 / 2 / 4 / 8 on 32 -> 64 at 320^2: fwd 253 / 235 / 260 / 261 us, dgrad 218 / 209 / 214 / 224
     static bool attr_done = false;
     if (!attr_done) {
-        (void)hipFuncSetAttribute((const void*)pconv_kernel<CS, BN, NSL, EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
+        (void)hipFuncSetAttribute((const void*)patch_kernel<G, CS, BN, NSL, EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, L::SMEM);
         attr_done = true;
     }
-    hipLaunchKernelGGL((pconv_kernel<CS, BN, NSL, EPI>), dim3(blocks), dim3(256), smem, s, p);
-    FVA_LAUNCH_CHECK("pconv_kernel");
-    fva_note_kernel("pconv");
+    hipLaunchKernelGGL((patch_kernel<G, CS, BN, NSL, EPI>), dim3(cdiv(tiles, p.pt_tpb)), dim3(256), L::SMEM, s, p);
+    FVA_LAUNCH_CHECK(G::KERNEL);
+    fva_note_kernel(G::LABEL);
     return FVA_OK;
 }
 
-// p is set up as for igemm (in / wt / out / N / C / in_row / in_img / y0 / x0 / epilogue fields); H, W = output image; flip: data gradient
 template <int EPI>
-int launch_pconv(const IgemmParams& p0, int B, int H, int W, bool flip, hipStream_t s) {
+int PconvGeom::launch_form(const IgemmParams& p, int tiles, hipStream_t s) {
+    if (p.C == 32 && p.N == 64) return launch_patch_one<PconvGeom, 32, 64, 1, EPI>(p, tiles, s);
+    if (p.C == 64 && p.N == 32) return launch_patch_one<PconvGeom, 64, 32, 1, EPI>(p, tiles, s);
+    if (p.C == 64 && p.N == 64) return launch_patch_one<PconvGeom, 64, 64, 1, EPI>(p, tiles, s);
+    if (p.C == 64 && p.N == 128) return launch_patch_one<PconvGeom, 64, 128, 1, EPI>(p, tiles, s);
+    if (p.C == 128 && p.N == 64) return launch_patch_one<PconvGeom, 64, 64, 2, EPI>(p, tiles, s);
+    return fva_fail(FVA_ERR_ARG, "pconv: unsupported channels %d -> %d", p.C, p.N);
+}
+template <int EPI>
+int Pdgrad2Geom::launch_form(const IgemmParams& p, int tiles, hipStream_t s) {
+    if (p.C == 64 && p.N == 32) return launch_patch_one<Pdgrad2Geom, 64, 32, 1, EPI>(p, tiles, s);
+    if (p.C == 128 && p.N == 64) return launch_patch_one<Pdgrad2Geom, 64, 64, 2, EPI>(p, tiles, s);
+    return fva_fail(FVA_ERR_ARG, "pdgrad2: unsupported channels %d -> %d", p.C, p.N);
+}
+
+// p is set up as for igemm (in / wt / out / N / C / in_row / in_img / y0 / x0 / epilogue fields); H, W = output image.
+// PconvGeom: flip for the data gradient.  Pdgrad2Geom: in = dy halo buffer (y0 = x0 = dy_pad), wt = [9][Cin][Cout], out = dx dense,
+// N = Cin, C = Cout, H, W = the dx image.
+template <typename G, int EPI>
+int launch_patch(const IgemmParams& p0, int B, int H, int W, bool flip, hipStream_t s) {
     IgemmParams p = p0;
     p.pt_H = H;
     p.pt_W = W;
-    p.pt_tx = cdiv(W, 32);
-    p.pt_ty = cdiv(H, 8);
+    p.pt_tx = cdiv(W, 1 << G::TW_LOG2);
+    p.pt_ty = cdiv(H, G::TH);
     p.pt_div_tx = make_fastdiv(p.pt_tx);
     p.pt_div_img = make_fastdiv(p.pt_tx * p.pt_ty);
     for (int t = 0; t < 9; ++t) p.tap_w[t] = flip ? 8 - t : t;     // patch tap (dy, dx) <-> filter tap: the data gradient flips both axes
-    const int tiles = pconv_tiles(B, H, W);
-    if (p.C == 32 && p.N == 64) return launch_pconv_one<32, 64, 1, EPI>(p, tiles, s);
-    if (p.C == 64 && p.N == 32) return launch_pconv_one<64, 32, 1, EPI>(p, tiles, s);
-    if (p.C == 64 && p.N == 64) return launch_pconv_one<64, 64, 1, EPI>(p, tiles, s);
-    if (p.C == 64 && p.N == 128) return launch_pconv_one<64, 128, 1, EPI>(p, tiles, s);
-    if (p.C == 128 && p.N == 64) return launch_pconv_one<64, 64, 2, EPI>(p, tiles, s);
-    return fva_fail(FVA_ERR_ARG, "pconv: unsupported channels %d -> %d", p.C, p.N);
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// Patch form of the STRIDE-2 data gradient of the thin 3x3 layers (64 -> 32 channels at 640^2, 128 -> 64 at 320^2; bf16).
-//   dx[2i + py][2j + px] = sum over the taps (kh, kw) with kh = 1 (py = 0) or kh in {0, 2} (py = 1), likewise kw / px, of
-//                          dy[i + (kh == 0)][j + (kw == 0)] . W[kh][kw]
-// Until round 3 these ran as two "paired" implicit-GEMM launches (both x parities as N' = 2 Cin columns: 4/3 of the MACs, every
-// tap's dy tile fetched again) -- 505 / 330 us for 1.26 / 1.05 GB of HBM traffic.  Here a block owns 4 x 32 cells = 8 x 64 dx
-// pixels: the (4+1) x (32+1) dy pixels they need are staged once (21 KiB per 64-channel slice), every tap is ONE shifted fragment
-// read feeding exactly the parity class it belongs to (the exact 9/4 MACs per dx pixel), wave w owns cell row w with eight
-// accumulator groups (4 parity classes x 2 halves of the row).  Weights: the plain [9][Cin][Cout] dgrad layout, resident (36 KiB)
-// or streamed through two slots like pconv_kernel; epilogue / statistics / store loop are the shared ones (512-row tile).
-template <int CS, int BN, int NSL, int EPI>
-__global__ __launch_bounds__(256, 2) void pdgrad2_kernel(const IgemmParams p) {
-    constexpr int CH = 4, CW = 32, PW = CW + 1, NPIX = (CH + 1) * PW;             // 165 dy pixels
-    constexpr int PIXB = CS * 2, CPP = PIXB / 16, PPI = 1024 / PIXB;
-    static_assert(CS == 64, "64-channel slices (128-byte pixel rows)");
-    constexpr int PATCH_INSTR = (NPIX + PPI - 1) / PPI, PATCH_BYTES = PATCH_INSTR * 1024;
-    constexpr int WSTEP_BYTES = BN * PIXB, WPW = WSTEP_BYTES / 1024 / 4;
-    static_assert(WSTEP_BYTES % 4096 == 0, "whole DMA instructions per wave");
-    constexpr int STEPS = 9 * NSL;
-    constexpr bool RESIDENT = NSL == 1 && 9 * WSTEP_BYTES <= 36 * 1024;
-    constexpr int WBUF_BYTES = (RESIDENT ? 9 : 2) * WSTEP_BYTES;
-    constexpr bool LOOPED = RESIDENT && EPI != EPI_BNB;   // the fused-statistics epilogue inside the tile loop spills (35 registers): one tile per block there
-    constexpr int BM = 512, NT = 256, NTILE = BN / 16, KS = CS / 32;
-    constexpr int PITCH = BN * 2 + 16, TILE_BYTES = BM * PITCH;
-    constexpr int WOFF = RESIDENT && TILE_BYTES > PATCH_BYTES ? TILE_BYTES : PATCH_BYTES;
-    constexpr int COEF0 = TILE_BYTES > WOFF + WBUF_BYTES ? TILE_BYTES : WOFF + WBUF_BYTES;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    char* const patch = smem;
-    char* const wbuf = smem + WOFF;
-
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int r16 = lane & 15, g = lane >> 4;
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int xcd = bid & 7, xq = nwg >> 3, xr = nwg & 7;
-    const int tile0 = ((xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + (bid >> 3)) * (LOOPED ? p.pt_tpb : 1);
-    const int Hp = p.in_img / p.in_row, Wp = p.in_row;
-    float* coef_tab = (float*)(smem + COEF0);
-    if constexpr (EPI == EPI_BNB) bnb_fill_lds<BN, NT>(p, coef_tab, tid, 0);
-    int b = 0, ty = 0, tx = 0, yorg = 0, xorg = 0;
-
-    auto swz = [](int r) { return (r >> 1) & 7; };
-    auto stage_patch = [&](int slice) {
-        const bf16_t* src0 = (const bf16_t*)p.in + (int64_t)b * p.in_img * p.C + slice * CS;
-#pragma unroll
-        for (int i = 0; i < (PATCH_INSTR + 3) / 4; ++i) {
-            const int j = i * 4 + w;
-            if (j < PATCH_INSTR) {
-                int pix = j * PPI + lane / CPP;
-                pix = pix < NPIX ? pix : NPIX - 1;
-                const int py = (pix * 1986) >> 16, px = pix - py * PW;             // / 33, exact below 400
-                int iy = yorg + py, ix = xorg + px;
-                iy = iy < Hp ? iy : Hp - 1;
-                ix = ix < Wp ? ix : Wp - 1;
-                const int chunk = (lane % CPP) ^ swz(j * PPI + lane / CPP);
-                __builtin_amdgcn_global_load_lds(GLB_PTR(src0 + ((int64_t)iy * Wp + ix) * p.C + chunk * 8), LDS_PTR(patch + j * 1024), 16, 0, 0);
-            }
-        }
-    };
-    auto stage_w = [&](int step, char* dst) {                          // step = slice * 9 + tap (tap = kh * 3 + kw)
-        const int slice = step / 9, tap = step - slice * 9;
-        const bf16_t* src0 = (const bf16_t*)p.wt + (int64_t)tap * p.N * p.C + slice * CS;
-#pragma unroll
-        for (int i = 0; i < WPW; ++i) {
-            const int j = i * 4 + w;
-            const int n = j * PPI + lane / CPP;
-            const int nn = n < p.N ? n : p.N - 1;
-            const int chunk = (lane % CPP) ^ swz(n);
-            __builtin_amdgcn_global_load_lds(GLB_PTR(src0 + (int64_t)nn * p.C + chunk * 8), LDS_PTR(dst + j * 1024), 16, 0, 0);
-        }
-    };
-
-    f32x4 acc[4][2][NTILE];            // [parity class py * 2 + px][half of the cell row][n tile]
-    int pix0[2];
-    int opq = 0;
-    auto compute = [&](int tap, const char* wb) {
-        const int kh = tap / 3, kw = tap % 3;
-        const int cls = (kh == 1 ? 0 : 2) + (kw == 1 ? 0 : 1);
-        const int tapoff = (kh == 0 ? PW : 0) + (kw == 0 ? 1 : 0);
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-            bf16x8 af[2], bfr[NTILE];
-#pragma unroll
-            for (int xt = 0; xt < 2; ++xt) {
-                const int pix = pix0[xt] + tapoff;
-                af[xt] = *(const bf16x8*)(patch + pix * PIXB + (((ks * 4 + g) ^ swz(pix)) << 4));
-            }
-#pragma unroll
-            for (int nt = 0; nt < NTILE; ++nt) {
-                const int n = nt * 16 + r16 + opq;
-                bfr[nt] = *(const bf16x8*)(wb + n * PIXB + (((ks * 4 + g) ^ swz(n)) << 4));
-            }
-#pragma unroll
-            for (int xt = 0; xt < 2; ++xt)
-#pragma unroll
-                for (int nt = 0; nt < NTILE; ++nt) acc[cls][xt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[nt], af[xt], acc[cls][xt][nt], 0, 0, 0);   // swapped: foreach_acc
-        }
-    };
-
-    if constexpr (RESIDENT) {
-#pragma unroll
-        for (int t = 0; t < 9; ++t) stage_w(t, wbuf + t * WSTEP_BYTES);
-    }
-#pragma unroll 1
-    for (int it = 0; it < (LOOPED ? p.pt_tpb : 1); ++it) {
-    const int tile = tile0 + it;
-    if (tile >= p.pt_tiles) break;
-    b = (int)fd_div((uint32_t)tile, p.pt_div_img);
-    {
-        const int trem = tile - b * (p.pt_tx * p.pt_ty);
-        ty = (int)fd_div((uint32_t)trem, p.pt_div_tx);
-        tx = trem - ty * p.pt_tx;
-    }
-    yorg = p.y0 + ty * CH;                                             // first dy pixel of the patch in the padded dy buffer
-    xorg = p.x0 + tx * CW;
-    asm volatile("" : "+v"(opq));
-#pragma unroll
-    for (int xt = 0; xt < 2; ++xt) pix0[xt] = w * PW + xt * 16 + r16 + opq;
-#pragma unroll
-    for (int c = 0; c < 4; ++c)
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < NTILE; ++j) acc[c][i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    if constexpr (RESIDENT) {
-        stage_patch(0);
-        wait_vmcnt<0>();
-        __builtin_amdgcn_s_barrier();
-#pragma unroll
-        for (int t = 0; t < 9; ++t) compute(t, wbuf + t * WSTEP_BYTES);
-    } else {
-        stage_patch(0);
-        stage_w(0, wbuf);
-#pragma unroll 1
-        for (int sl = 0; sl < NSL; ++sl) {
-#pragma unroll
-            for (int t = 0; t < 9; ++t) {
-                const int s = sl * 9 + t;
-                wait_vmcnt<0>();
-                __builtin_amdgcn_s_barrier();
-                if (NSL > 1 && t == 0 && sl > 0) {
-                    stage_patch(sl);
-                    stage_w(s + 1, wbuf + ((s + 1) & 1) * WSTEP_BYTES);
-                    wait_vmcnt<WPW>();
-                    __builtin_amdgcn_s_barrier();
-                } else if (s + 1 < STEPS) {
-                    stage_w(s + 1, wbuf + ((s + 1) & 1) * WSTEP_BYTES);
-                }
-                compute(t, wbuf + (s & 1) * WSTEP_BYTES);
-            }
-        }
-    }
-    __syncthreads();   // LDS is free for the epilogue
-    // accumulator element (class (py, px), half xt, j) = dx pixel (2 w + py, 2 (16 xt + 4 g + j) + px) of the 8 x 64 tile
-#pragma unroll
-    for (int c = 0; c < 4; ++c)
-#pragma unroll
-        for (int xt = 0; xt < 2; ++xt)
-#pragma unroll
-            for (int nt = 0; nt < NTILE; ++nt) {   // MFMA operands swapped (foreach_acc): lane (r16, g) holds cell xt * 16 + r16, channels nt * 16 + 4 g .. + 3
-                const f32x4 v = acc[c][xt][nt];
-                *(u32x2*)(smem + ((2 * w + (c >> 1)) * 64 + 2 * (xt * 16 + r16) + (c & 1)) * PITCH + (nt * 16 + 4 * g) * 2) = u32x2{cvt_pk_bf16(v[0], v[1]), cvt_pk_bf16(v[2], v[3])};
-            }
-    __syncthreads();
-    store_tile_bf16<EPI, BM, BN, NT, PITCH>(p, smem, tid, 0, tile, [&](int rr) -> int64_t {
-        const int oy = ty * 2 * CH + (rr >> 6), ox = tx * 2 * CW + (rr & 63);
-        return oy < p.pt_H && ox < p.pt_W ? ((int64_t)b * p.pt_H + oy) * p.pt_W + ox : (int64_t)-1;
-    }, nullptr, nullptr, EPI == EPI_BNB ? coef_tab : nullptr);
-    __syncthreads();
-    }
-}
-
-// stride-2 3x3 bf16 data gradients served by pdgrad2_kernel: reduction over C = Cout channels, N = Cin outputs.  Decided by the
-// channel counts alone (the weight packer must know the layout without seeing a feature-map size: these layers take the plain
-// [9][Cin][Cout] dgrad weights, the other thin stride-2 layers the paired layout).  FVA_PDGRAD2=0 switches it off.
-inline bool use_pdgrad2(int dtype, int ksize, int stride, int C, int N) {
-    static const bool on = [] { const char* e = getenv("FVA_PDGRAD2"); return !e || atoi(e) != 0; }();
-    return on && dtype == FVA_BF16 && ksize == 3 && stride == 2 && ((C == 64 && N == 32) || (C == 128 && N == 64));
-}
-inline int pdgrad2_tiles(int B, int H, int W) { return B * cdiv(H, 8) * cdiv(W, 64); }   // H, W: the dx image
-
-template <int CS, int BN, int NSL, int EPI>
-int launch_pdgrad2_one(const IgemmParams& p0, int tiles, hipStream_t s) {
-    constexpr int PIXB = CS * 2, PPI = 1024 / PIXB, PATCH_BYTES = ((165 + PPI - 1) / PPI) * 1024, WSTEP = BN * PIXB;
-    constexpr bool RESIDENT = NSL == 1 && 9 * WSTEP <= 36 * 1024;
-    constexpr int WBUF = (RESIDENT ? 9 : 2) * WSTEP, TILE = 512 * (BN * 2 + 16);
-    constexpr int WOFF = RESIDENT && TILE > PATCH_BYTES ? TILE : PATCH_BYTES;
-    constexpr int smem = (TILE > WOFF + WBUF ? TILE : WOFF + WBUF) + (EPI == EPI_BNB ? 4 * BN * 4 : 0);
-    static_assert(smem <= 80 * 1024, "two blocks per CU");
-    static const int tpb_env = [] { const char* e = getenv("FVA_PCONV_TPB"); return e ? atoi(e) : 0; }();
-    IgemmParams p = p0;
-    p.pt_tiles = tiles;
-    p.pt_tpb = RESIDENT && EPI != EPI_BNB ? (tpb_env > 0 ? tpb_env : 2) : 1;
-    static bool attr_done = false;
-    if (!attr_done) {
-        (void)hipFuncSetAttribute((const void*)pdgrad2_kernel<CS, BN, NSL, EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-        attr_done = true;
-    }
-    hipLaunchKernelGGL((pdgrad2_kernel<CS, BN, NSL, EPI>), dim3(cdiv(tiles, p.pt_tpb)), dim3(256), smem, s, p);
-    FVA_LAUNCH_CHECK("pdgrad2_kernel");
-    fva_note_kernel("pdgrad2");
-    return FVA_OK;
-}
-
-// p: in = dy halo buffer (in_row / in_img / y0 = x0 = dy_pad), wt = [9][Cin][Cout], out = dx dense, N = Cin, C = Cout; H, W = dx image
-template <int EPI>
-int launch_pdgrad2(const IgemmParams& p0, int B, int H, int W, hipStream_t s) {
-    IgemmParams p = p0;
-    p.pt_H = H;
-    p.pt_W = W;
-    p.pt_tx = cdiv(W, 64);
-    p.pt_ty = cdiv(H, 8);
-    p.pt_div_tx = make_fastdiv(p.pt_tx);
-    p.pt_div_img = make_fastdiv(p.pt_tx * p.pt_ty);
-    const int tiles = pdgrad2_tiles(B, H, W);
-    if (p.C == 64 && p.N == 32) return launch_pdgrad2_one<64, 32, 1, EPI>(p, tiles, s);
-    if (p.C == 128 && p.N == 64) return launch_pdgrad2_one<64, 64, 2, EPI>(p, tiles, s);
-    return fva_fail(FVA_ERR_ARG, "pdgrad2: unsupported channels %d -> %d", p.C, p.N);
+    return G::template launch_form<EPI>(p, patch_tiles<G>(B, H, W), s);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -2123,7 +1985,7 @@ int fva_conv_pack_weights_tiled(const fva_pack_entry* table_dev, int32_t n, int3
 
 int32_t fva_conv_stat_blocks(const fva_conv_desc* d) {
     if (!d) return 0;
-    if (use_pconv(d->dtype, d->ksize, d->stride, d->Cin, d->Cout, d->H, d->W)) return pconv_tiles(d->B, d->H, d->W);
+    if (use_pconv(d->dtype, d->ksize, d->stride, d->Cin, d->Cout, d->H, d->W)) return patch_tiles<PconvGeom>(d->B, d->H, d->W);
     const int OH = (d->H - 1) / d->stride + 1, OW = (d->W - 1) / d->stride + 1;
     const int64_t M = (int64_t)d->B * OH * OW;
     const int64_t in_img = (int64_t)(d->H + 2 * d->in_pad) * (d->W + 2 * d->in_pad);
@@ -2177,7 +2039,7 @@ int fva_conv_fwd(const fva_conv_desc* d, const void* x, const void* w_fwd, void*
     p.out = y;
     p.stats = stats_partial;
     FvaProfileSpan span(0 | (d->ksize << 8), 2.0 * p.M * (double)d->Cout * d->Cin * d->ksize * d->ksize, (hipStream_t)stream);
-    if (use_pconv(d->dtype, d->ksize, d->stride, d->Cin, d->Cout, d->H, d->W)) return launch_pconv<EPI_STATS>(p, d->B, d->H, d->W, false, (hipStream_t)stream);
+    if (use_pconv(d->dtype, d->ksize, d->stride, d->Cin, d->Cout, d->H, d->W)) return launch_patch<PconvGeom, EPI_STATS>(p, d->B, d->H, d->W, false, (hipStream_t)stream);
     return launch_igemm<EPI_STATS>(d->dtype, p, (hipStream_t)stream);
 }
 
@@ -2238,7 +2100,7 @@ int fva_conv_fwd_acc(const fva_conv_desc* d, const void* x, const void* w_fwd, v
     p.stats_acc = (long long*)acc;
     p.acc_rep = replicas;
     FvaProfileSpan span(0 | (d->ksize << 8), 2.0 * p.M * (double)d->Cout * d->Cin * d->ksize * d->ksize, (hipStream_t)stream);
-    if (use_pconv(d->dtype, d->ksize, d->stride, d->Cin, d->Cout, d->H, d->W)) return launch_pconv<EPI_STATS>(p, d->B, d->H, d->W, false, (hipStream_t)stream);
+    if (use_pconv(d->dtype, d->ksize, d->stride, d->Cin, d->Cout, d->H, d->W)) return launch_patch<PconvGeom, EPI_STATS>(p, d->B, d->H, d->W, false, (hipStream_t)stream);
     return launch_igemm<EPI_STATS>(d->dtype, p, (hipStream_t)stream);
 }
 
@@ -2336,10 +2198,10 @@ int32_t fva_conv_dgrad_stat_rows(const fva_conv_desc* d) {
     const int k = d->ksize, s = d->stride;
     const int OH = (d->H - 1) / s + 1, OW = (d->W - 1) / s + 1;
     const int64_t in_pixels = (int64_t)(d->B + 1) * (OH + 2 * d->dy_pad) * (OW + 2 * d->dy_pad);
-    if (use_pconv(d->dtype, k, s, d->Cout, d->Cin, d->H, d->W)) return pconv_tiles(d->B, d->H, d->W);
+    if (use_pconv(d->dtype, k, s, d->Cout, d->Cin, d->H, d->W)) return patch_tiles<PconvGeom>(d->B, d->H, d->W);
     if (s == 1) return dgrad_launch_rows(d, (int64_t)d->B * d->H * d->W, d->Cin, d->Cout, k * k, in_pixels);
     const int64_t mq = (int64_t)d->B * (d->H / 2) * (d->W / 2);
-    if (use_pdgrad2(d->dtype, k, s, d->Cout, d->Cin)) return pdgrad2_tiles(d->B, d->H, d->W);
+    if (use_pdgrad2(d->dtype, k, s, d->Cout, d->Cin)) return patch_tiles<Pdgrad2Geom>(d->B, d->H, d->W);
     if (dgrad_paired(d->dtype, k, s, d->Cin, d->Cout)) {   // two launches (row parity) of N' = 2 * Cin columns: two table rows per block
         int rows = 0;
         for (int py = 0; py < 2; ++py) rows += 2 * dgrad_launch_rows(d, mq, 2 * d->Cin, d->Cout, py == 0 ? 2 : 4, in_pixels);
@@ -2408,14 +2270,14 @@ int fva_conv_dgrad_bnstats(const fva_conv_desc* d, const void* dy, const void* w
         finish_taps(p, nt, d->dtype);
         p.out_dense = 1;
         if (use_pconv(d->dtype, k, s, d->Cout, d->Cin, d->H, d->W))
-            return f ? launch_pconv<EPI_BNB>(p, d->B, d->H, d->W, true, (hipStream_t)stream) : launch_pconv<EPI_PLAIN>(p, d->B, d->H, d->W, true, (hipStream_t)stream);
+            return f ? launch_patch<PconvGeom, EPI_BNB>(p, d->B, d->H, d->W, true, (hipStream_t)stream) : launch_patch<PconvGeom, EPI_PLAIN>(p, d->B, d->H, d->W, true, (hipStream_t)stream);
         return f ? launch_igemm<EPI_BNB>(d->dtype, p, (hipStream_t)stream) : launch_igemm<EPI_PLAIN>(d->dtype, p, (hipStream_t)stream);
     }
     const int JH = d->H / 2, JW = d->W / 2;
     if (use_pdgrad2(d->dtype, k, s, d->Cout, d->Cin)) {
         p.y0 = p.x0 = d->dy_pad;          // dy pixel (i, j) sits at padded (i + pad, j + pad); rows / columns up to OH / OW are the zero halo
         p.out_dense = 1;
-        return f ? launch_pdgrad2<EPI_BNB>(p, d->B, d->H, d->W, (hipStream_t)stream) : launch_pdgrad2<EPI_PLAIN>(p, d->B, d->H, d->W, (hipStream_t)stream);
+        return f ? launch_patch<Pdgrad2Geom, EPI_BNB>(p, d->B, d->H, d->W, false, (hipStream_t)stream) : launch_patch<Pdgrad2Geom, EPI_PLAIN>(p, d->B, d->H, d->W, false, (hipStream_t)stream);
     }
     if (dgrad_paired(d->dtype, k, s, d->Cin, d->Cout)) {
         // thin layers: both x-parities of an output row per launch (see dgrad_paired) -- 2 launches, N' = 2*Cin

@@ -25,6 +25,7 @@ CASES = [
     (1, 256, 128, 13, 13, 1, 1),     # 1x1, two column blocks
     (3, 128, 128, 8, 12, 3, 2),      # stride 2: four parity launches
     (2, 64, 128, 16, 16, 3, 2),      # stride 2, thin: the stride-2 patch kernel in bf16 (two paired launches, N' = 2 * Cin, in fp32)
+    (2, 32, 64, 16, 16, 3, 2),       # the same with resident weights (C = 64 in one slice): one tile per block, the 8 x 64 tile overhangs in x
     (8, 256, 512, 64, 64, 3, 1),     # 8-phase 256x256 kernel (bf16): 128 tiles, 72 k-tiles
 ]
 

@@ -467,7 +467,7 @@ def test_gather_cast_fills_a_gradient_bucket(wire):
 
 @pytest.mark.parametrize('case', [(2, 32, 64, 64, 96), (1, 64, 128, 70, 72), (1, 128, 64, 66, 64), (1, 64, 64, 64, 65)])
 def test_patch_kernel_against_the_implicit_gemm_kernels(case):
-    """pconv_kernel (thin 3x3 stride-1 bf16 layers: the patch of an 8 x 32 output tile staged once for the nine taps) against the
+    """The patch kernel in its stride-1 geometry ("pconv"; thin 3x3 stride-1 bf16 layers: the patch of an 8 x 32 output tile staged once for the nine taps) against the
     implicit-GEMM kernels it replaces on the same inputs, switched in-process (fva_conv_patch_kernel): forward tile + BatchNorm
     statistics, dgrad with the residual addend, dgrad with the fused BatchNorm-backward statistics.  Same products, another summation
     order: outputs agree to bf16 rounding of the stored value (one ulp = 2^-8 relative), column sums of the statistics to 1e-4."""
