@@ -60,8 +60,22 @@ __global__ __launch_bounds__(256) void roi_align_kernel(const RoiParams p) {
     const int lane_c = threadIdx.x & (RC - 1), sub = threadIdx.x >> 6;   // 4 bins in parallel
     const int c = c0 + lane_c;
     const float* roi = p.rois + (int64_t)k * 5;
-    const int b = (int)roi[0];
-    if (b < 0 || b >= p.B) return;                                       // uniform per block
+    // the image index is tested as a float: NaN fails both comparisons, and 1e9 never reaches the int conversion.  A box without
+    // an image (uniform per block) pools nothing: its slice of the output is written as zeros (the caller allocates with
+    // torch.empty), and it adds nothing to the gradient.
+    const float bf = roi[0];
+    if (!(bf >= 0.f && bf < (float)p.B)) {
+        if constexpr (!BWD) {
+            const int row = p.PH * p.PW, cmax = min(RC, p.C - c0);
+            float* o = p.out + ((int64_t)k * p.C + c0) * row + blockIdx.z * p.PW;
+            for (int e = threadIdx.x; e < cmax * p.PW; e += 256) {
+                const int cc = e / p.PW;
+                o[(int64_t)cc * row + (e - cc * p.PW)] = 0.f;
+            }
+        }
+        return;
+    }
+    const int b = (int)bf;
     const float x1 = roi[1] * p.scale, y1 = roi[2] * p.scale, x2 = roi[3] * p.scale, y2 = roi[4] * p.scale;
     const float roi_w = fmaxf(x2 - x1, 1.f), roi_h = fmaxf(y2 - y1, 1.f);
     const float bin_h = roi_h / (float)p.PH, bin_w = roi_w / (float)p.PW;

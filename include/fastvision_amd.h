@@ -604,7 +604,8 @@ int fva_fast_match(const float* proposals_xywh, int32_t N, const float* targets,
  * index, x1, y1, x2, y2), out [K][C][PH][PW] fp32 (the order torch.flatten(.., 1) feeds the classifier), aligned = False,
  * sampling_ratio <= 0 = adaptive grid.  feat: halo NHWC [B][H+2*feat_pad][W+2*feat_pad][C] of dtype.  Backward: grad_out in
  * the same [K][C][PH][PW] layout is scattered (float atomics) into dfeat, dense fp32 NHWC [B][H][W][C], which the caller
- * zeroes first.  K = 0 is a no-op. */
+ * zeroes first.  K = 0 is a no-op.  A box whose batch index is not in [0, B) -- NaN included -- pools nothing: its out rows are
+ * written as zeros, and it adds nothing to dfeat. */
 int fva_roi_align_fwd(int dtype, const void* feat, int feat_pad, const float* rois, int K, float* out, int B, int H, int W, int C,
                       int PH, int PW, float spatial_scale, int sampling_ratio, void* stream);
 int fva_roi_align_bwd(const float* grad_out, const float* rois, int K, float* dfeat, int B, int H, int W, int C, int PH, int PW,

@@ -1,4 +1,5 @@
-"""RoIAlign HIP kernel (scope row f-4) against the CPU restatement, through the C ABI (fastvision_amd.roi_ops)."""
+"""RoIAlign HIP kernel (scope row f-4) against the CPU restatement, through the C ABI (fastvision_amd.roi_ops); from
+test_every_element_forward_and_backward on, element by element against float64 sums over the taps (tests/roi_restatement.py)."""
 import numpy as np
 import pytest
 import torch
@@ -111,3 +112,77 @@ def test_non_finite_and_huge_boxes_terminate():
     assert out.shape == (4, 64, 7, 7)
     with pytest.raises(ValueError):
         roi_align(feat.to(DEV), torch.from_numpy(boxes[:1]).to(DEV), (7, 7), sampling_ratio=100)
+
+
+# ------------------------------------------------------------------------------------------------ element by element (tests/roi_restatement.py)
+import roi_restatement as rr  # noqa: E402
+import streaming_measure as sm  # noqa: E402
+
+
+@pytest.mark.parametrize('case', rr.CASES, ids=[f'scale{c[0]}_ratio{c[1]}_{c[2][0]}x{c[2][1]}_C{c[3]}_{"bf16" if c[5] else "fp32"}' for c in rr.CASES])
+def test_every_element_forward_and_backward(case):
+    """Every output element against the float64 sum over its taps, every gradient element against the float64 sum of its contributions
+    (limits: tests/roi_restatement.py), with spatial_scale != 1, fixed sampling grids, PW > 49 (the second pass), samples exactly on -1, 0,
+    size - 1 and size, a box of zero size, a box outside the map (exact zeros) and two identical boxes (their gradients add)."""
+    from fastvision_amd.roi_ops import roi_align
+    scale, sampling, osz, C, (H, W), bf16 = case
+    g = torch.Generator().manual_seed(31 + C)
+    feat = torch.randn(rr.BATCH, C, H, W, generator=g)
+    feat = feat.bfloat16() if bf16 else feat
+    boxes, exact = rr.edge_boxes(rr.BATCH, H, W, osz, scale, sampling)
+    for row, axis, bins, target in exact:
+        lo, hi = (boxes[row, 2], boxes[row, 4]) if axis == 0 else (boxes[row, 1], boxes[row, 3])
+        assert rr.first_sample(lo, hi, bins, scale, sampling) == np.float32(target)
+    f_dev = feat.to(DEV).requires_grad_(True)
+    out = roi_align(f_dev, torch.from_numpy(boxes).to(DEV), osz, scale, sampling)
+    ref, lim = rr.forward_reference(feat, boxes, osz, scale, sampling)
+    assert out.dtype == torch.float32 and out.shape == ref.shape
+    wf = sm.worst_f32(out.detach().cpu(), ref, lim)
+    go = torch.randn(ref.shape, generator=g)
+    out.backward(go.to(DEV))
+    dref, dlim = rr.backward_reference(go, boxes, feat.shape, scale, sampling)
+    if bf16:
+        dlim = dlim + 0.5 * sm.bf16_ulp(dref)
+    assert f_dev.grad.dtype == feat.dtype
+    wb = sm.worst_f32(f_dev.grad.float().cpu(), dref, dlim)
+    print(f'roi_align {case}: worst err / limit forward {wf:.3f}, backward {wb:.3f}')
+    assert wf <= 1.0, f'forward: worst err / limit = {wf:.3f}'
+    assert wb <= 1.0, f'backward: worst err / limit = {wb:.3f}'
+
+
+@pytest.mark.parametrize('index', [-1.0, 2.0, 1e9, float('nan')], ids=['minus_one', 'B', '1e9', 'nan'])
+def test_box_without_an_image_gives_zeros_and_no_gradient(index):
+    """A box whose image index is not in [0, B): an all-zero output row whatever the allocation held before, the neighbouring rows as if it
+    were not there, and nothing added to the gradient.  C = 65 (a full and a one-channel slice), PW = 50 (both passes of bins)."""
+    import ctypes
+    from fastvision_amd import _lib
+    from fastvision_amd.ops import _code, _p, _stream, to_halo
+    from fastvision_amd.roi_ops import roi_align
+    B, C, H, W, osz = 2, 65, 5, 9, (2, 50)
+    g = torch.Generator().manual_seed(77)
+    feat = torch.randn(B, C, H, W, generator=g)
+    boxes, _ = rr.edge_boxes(B, H, W, osz, 1.0, 2)
+    bad = [0, 7, len(boxes) - 1]
+    good = [i for i in range(len(boxes)) if i not in bad]
+    boxes[bad, 0] = index
+    K = len(boxes)
+    # the kernel itself, on an output buffer that holds a pattern
+    keep, base, pad = to_halo(feat.to(DEV), torch.float32, 0)
+    rois = torch.from_numpy(boxes).to(DEV)
+    raw = torch.full((K, C) + osz, 123.0, device=DEV)
+    _lib.call('fva_roi_align_fwd', _code(torch.float32), ctypes.c_void_p(base), pad, _p(rois), K, _p(raw), B, H, W, C, osz[0], osz[1], 1.0, 2, _stream())
+    # and through roi_align, whose torch.empty most likely gets the block that was just freed
+    junk = [torch.full((K, C) + osz, float('nan'), device=DEV) for _ in range(3)]
+    del junk
+    f_dev = feat.to(DEV).requires_grad_(True)
+    out = roi_align(f_dev, rois, osz, 1.0, 2)
+    alone = roi_align(feat.to(DEV), rois[good], osz, 1.0, 2)
+    for o in (raw, out.detach()):
+        assert torch.all(o[bad] == 0), 'a box without an image must give zeros'
+        assert torch.equal(o[good], alone), 'the valid rows are unchanged'
+    ref, lim = rr.forward_reference(feat, boxes, osz, 1.0, 2)
+    assert sm.worst_f32(out.detach().cpu(), ref, lim) <= 1.0
+    go = torch.randn(ref.shape, generator=g)
+    out.backward(go.to(DEV))
+    dref, dlim = rr.backward_reference(go[good], boxes[good], feat.shape, 1.0, 2)
+    assert sm.worst_f32(f_dev.grad.cpu(), dref, dlim) <= 1.0
