@@ -1,0 +1,5 @@
+"""Shim: `data_gen` of the reference's demos/yolov3_huaweiShip resolves to `fastvision_amd.demos.yolov3_huaweiShip.data_gen` (the same module object)."""
+import importlib
+import sys
+
+sys.modules[__name__] = importlib.import_module('fastvision_amd.demos.yolov3_huaweiShip.data_gen')

@@ -146,6 +146,9 @@ PROTOTYPES = {
     'fva_rows_relu_bwd': (_I, [_I, _P, _P, _P, _L, _P, _I, _I, _I, _P]),
     'fva_demo_loss': (_I, [_P, _I, _H, _I, _P, _P, _L, _P]),
     'fva_demo_loss_workspace': (_L, [_I, _H, _I]),
+    'fva_demo_ciou_loss': (_I, [_P, _I, _H, _I, _P, _P, _L, _P]),
+    'fva_demo_ciou_loss_workspace': (_L, [_I, _H, _I]),
+    'fva_scale_head_groups': (_I, [_H, _P, _P, _P, _P]),
     'fva_iou_pairwise': (_I, [_I, _I, _I, _P, _P, _P, _P, _L, _F, _P]),
     'fva_iou_batch': (_I, [_I, _I, _I, _P, _P, _P, _L, _L, _F, _P]),
     'fva_adam_step': (_I, [_P, _P, _I, _L, _F, _F, _F, _F, _F, _L, _F, _P]),
@@ -195,7 +198,7 @@ LABEL_I64, LABEL_F32 = 0, 1
 REDUCE_MEAN, REDUCE_SUM = 0, 1
 UNCHECKED = {'fva_conv_patch_kernel', 'fva_sgd_chunk_elems', 'fva_rows_relu_bwd_rows', 'fva_colour_workspace', 'fva_conv_dgrad_stat_rows', 'fva_bias_relu_bwd_rows', 'fva_colsum_scratch_rows', 'fva_last_error', 'fva_version', 'fva_profile_stop', 'fva_conv_last_kernel', 'fva_conv_packed_elems', 'fva_conv_stat_blocks', 'fva_conv_wgrad_workspace', 'fva_conv_wgrad_plan',
              'fva_stem_stat_blocks', 'fva_stem_fused_blocks', 'fva_stem_wgrad_workspace', 'fva_stem_fwd_workspace', 'fva_stem_wgrad_mfma_workspace', 'fva_bn_bwd_blocks', 'fva_bn_partial_rows', 'fva_yolov3_loss_workspace',
-             'fva_demo_loss_workspace', 'fva_nms_candidates_workspace', 'fva_nms_select_workspace', 'fva_softmax_ce_workspace'}
+             'fva_demo_loss_workspace', 'fva_demo_ciou_loss_workspace', 'fva_nms_candidates_workspace', 'fva_nms_select_workspace', 'fva_softmax_ce_workspace'}
 
 _lib = None
 

@@ -48,7 +48,7 @@ __global__ __launch_bounds__(256) void decode_kernel(const DecodeParams kp, floa
     const int a = rr - c * lv.A;
     const int y = (int)fd_div((uint32_t)c, p.div_w[l]);
     const int x = c - y * lv.W;
-    // output row: (a, y, x) for the library variant, (y, x, a) for the demo
+    // output row: (a, y, x) for the library variant, (y, x, a) for the two demos
     const int orow = p.row0[l] + (p.variant == 0 ? a * lv.H * lv.W + c : rr);
     const int64_t i = ((int64_t)b * p.rows + orow) * p.K + k;
     const float* src = lv.data + b * lv.sb + a * lv.sa + y * lv.sy + x * lv.sx;
@@ -56,16 +56,17 @@ __global__ __launch_bounds__(256) void decode_kernel(const DecodeParams kp, floa
     auto centre = [&](int axis) {
         const float cell = axis ? (float)y : (float)x;
         const float s = sigmoid_acc(src[axis * lv.sk]);
-        return p.variant == 0 ? (s + cell) * lv.stride : (s * 2.f - 0.5f + cell) * lv.stride;
+        return p.variant == 1 ? (s * 2.f - 0.5f + cell) * lv.stride : (s + cell) * lv.stride;
     };
     auto extent = [&](int axis) {
         const float anc = axis ? lv.anchor_h[a] : lv.anchor_w[a];
         const float t = src[(2 + axis) * lv.sk];
         if (p.variant == 0) return expf(t) * anc;
+        if (p.variant == 2) return expf(t) * anc * lv.stride;  // ship demo (demos/yolov3_huaweiShip/inference.py:113-114)
         const float s2 = sigmoid_acc(t) * 2.f;
         return s2 * s2 * anc * lv.stride;
     };
-    // demo postProcess (inference.py:90-106): undo the letterbox, clamp to the original image
+    // demo postProcess (inference.py:90-106; the ship demo's :119-136 is the same): undo the letterbox, clamp to the original image
     auto extent_ori = [&](int axis) { return clampf(extent(axis) / p.lb.resize_ratio, 0.f, axis ? p.lb.ori_h : p.lb.ori_w); };
     if (k >= 4) {
         float v = sigmoid_acc(src[k * lv.sk]);
@@ -318,8 +319,8 @@ extern "C" int fva_yolo_decode(const fva_head_level* levels, int32_t nlevels, in
                                float* out, int64_t rows_per_image, void* stream) {
     if (!levels || !out) return fva_fail(FVA_ERR_ARG, "fva_yolo_decode: null pointer");
     if (nlevels < 1 || nlevels > MAX_LEVELS) return fva_fail(FVA_ERR_ARG, "fva_yolo_decode: nlevels %d not in 1..%d", nlevels, MAX_LEVELS);
-    if (variant != 0 && variant != 1) return fva_fail(FVA_ERR_ARG, "fva_yolo_decode: bad variant %d", variant);
-    if (lb && variant != 1) return fva_fail(FVA_ERR_ARG, "fva_yolo_decode: the letterbox mapping belongs to the demo variant");
+    if (variant < 0 || variant > 2) return fva_fail(FVA_ERR_ARG, "fva_yolo_decode: bad variant %d", variant);
+    if (lb && variant == 0) return fva_fail(FVA_ERR_ARG, "fva_yolo_decode: the letterbox mapping belongs to the demo variants");
     DecodeParams p{};
     int64_t rows = 0;
     for (int l = 0; l < nlevels; ++l) {

@@ -456,6 +456,61 @@ __global__ __launch_bounds__(256) void demo_target_kernel(const float* __restric
     }
 }
 
+// the ship demo's form of the same kernel (demos/yolov3_huaweiShip/utils/lossv3.py:35-95): best anchor and cell as above, the class term
+// across the lanes, and on lane 0 the box term 1 - CIoU(pred, target; 'xywh') of the demo's CIoU (centre sums not halved, minus sign), with
+// pred = (sigmoid(z_xy) + cell, exp(z_wh) * anchor).  d (1 - CIoU) / d (x, y, w, h) comes from the forward-mode duals, followed by
+// dx/dz = s (1 - s) and dw/dz = w.  db.l_xy holds the box terms; db.l_wh is not used.
+__global__ __launch_bounds__(256) void ship_target_kernel(const float* __restrict__ tg, int T, const Level lv, const DemoBuf db) {
+    const int lane = threadIdx.x & 63, wpb = blockDim.x >> 6;
+    const int C = lv.K - 5;
+    for (int t = blockIdx.x * wpb + (threadIdx.x >> 6); t < T; t += gridDim.x * wpb) {
+        const float fw = (float)lv.W, fh = (float)lv.H;
+        const float tx = tg[t * 6 + 2] * fw, ty = tg[t * 6 + 3] * fh, tw = tg[t * 6 + 4] * fw, th = tg[t * 6 + 5] * fh;
+        int best = 0;
+        float best_iou = -INFINITY;
+        for (int a = 0; a < lv.A; ++a) {  // wh_iou_batch (iou.py:177-189) + torch.max first index
+            const float inter = fminf(tw, lv.aw[a]) * fminf(th, lv.ah[a]);
+            const float iou = inter / (((tw * th) + (lv.aw[a] * lv.ah[a])) - inter + IOU_EPS);
+            if (iou > best_iou) { best_iou = iou; best = a; }
+        }
+        const float gxf = floorf(tx), gyf = floorf(ty);
+        const int b = (int)tg[t * 6], gx = (int)gxf, gy = (int)gyf, cls = (int)tg[t * 6 + 1];
+        const bool ok = b >= 0 && b < lv.B && gx >= 0 && gx < lv.W && gy >= 0 && gy < lv.H;  // reference: IndexError otherwise
+        if (!ok) {
+            if (lane == 0) { db.l_xy[t] = 0.f; db.l_cls[t] = 0.f; db.cell[t] = -1; }
+            continue;
+        }
+        const int64_t base = b * lv.sb + best * lv.sa + gy * lv.sy + gx * lv.sx;
+        float lsum = 0.f;
+        const float gcls = 1.f / ((float)T * (float)C);
+        for (int k = lane; k < C; k += 64) {
+            const float z = lv.data[base + (5 + k) * lv.sk];
+            const float tt = (k == cls) ? 1.f : 0.f;
+            lsum += bce_logits(z, tt);
+            if (lv.grad) atomicAdd(&lv.grad[base + (5 + k) * lv.sk], (sigm(z) - tt) * gcls);
+        }
+        lsum = wave_sum(lsum);
+        if (lane == 0) {
+            const float z0 = lv.data[base], z1 = lv.data[base + lv.sk], z2 = lv.data[base + 2 * lv.sk], z3 = lv.data[base + 3 * lv.sk];
+            const float sx = sigm(z0), sy = sigm(z1);
+            const float px = sx + gxf, py = sy + gyf;  // :65-69
+            const float pw = expf(z2) * lv.aw[best], ph = expf(z3) * lv.ah[best];
+            const BoxD pb = xywh2xyxy_d(dvar(px, 0), dvar(py, 1), dvar(pw, 2), dvar(ph, 3));
+            const BoxD tb = xywh2xyxy_d(dconst(tx), dconst(ty), dconst(tw), dconst(th));
+            const D4 ciou = ciou_d(pb, tb, IOU_EPS, 1, nullptr);  // :87
+            db.l_xy[t] = 1.f - ciou.v;
+            db.l_cls[t] = lsum;
+            db.cell[t] = ((b * lv.H + gy) * lv.W + gx) * lv.A + best;
+            if (lv.grad) {
+                const float gb = 1.f / (float)T;  // :88 mean over the targets
+                const float dpdz[4] = {sx * (1.f - sx), sy * (1.f - sy), pw, ph};
+#pragma unroll
+                for (int i = 0; i < 4; ++i) atomicAdd(&lv.grad[base + i * lv.sk], -(ciou.d[i] * dpdz[i]) * gb);
+            }
+        }
+    }
+}
+
 // ignore mask (lossv3.py:86-100): per predicted box, max IoU against the targets of its image > 0.5 -> -1
 __global__ __launch_bounds__(256) void demo_mask_kernel(const float* __restrict__ tg, const Level lv, const DemoBuf db) {
     const int64_t n = (int64_t)lv.B * lv.H * lv.W * lv.A;
@@ -534,6 +589,28 @@ __global__ __launch_bounds__(256) void demo_level_final_kernel(const DemoBuf db,
         if (last) {
             out[1] = (float)acc[0]; out[2] = (float)acc[1]; out[3] = (float)acc[2]; out[4] = (float)acc[3];
             out[0] = (float)(acc[0] * 2.0 + acc[1] + acc[2] + acc[3]);
+        }
+    }
+}
+
+// the same finish for the ship demo's three parts (box terms in db.l_xy): acc[3] accumulates across levels
+__global__ __launch_bounds__(256) void ship_level_final_kernel(const DemoBuf db, int T, int C, int blocks, double* acc, float* out,
+                                                               int last) {
+    __shared__ double red[4][256];
+    double s[4] = {0, 0, 0, 0};
+    for (int i = threadIdx.x; i < T; i += 256) { s[0] += db.l_xy[i]; s[1] += db.l_cls[i]; }
+    for (int i = threadIdx.x; i < blocks; i += 256) { s[2] += db.conf_part[2 * i]; s[3] += db.conf_part[2 * i + 1]; }
+    for (int k = 0; k < 4; ++k) red[k][threadIdx.x] = s[k];
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int k = 0; k < 4; ++k) { s[k] = 0; for (int i = 0; i < 256; ++i) s[k] += red[k][i]; }
+        *db.nvalid = (float)s[3];
+        acc[0] += s[0] / (double)T;
+        acc[1] += s[1] / ((double)T * C);
+        acc[2] += s[2] / s[3];
+        if (last) {
+            out[1] = (float)acc[0]; out[2] = (float)acc[1]; out[3] = (float)acc[2];
+            out[0] = (float)(acc[0] + acc[1] + acc[2]);
         }
     }
 }
@@ -725,6 +802,33 @@ __global__ __launch_bounds__(256) void scale_by_scalar_kernel(float* __restrict_
     if (blockIdx.x == 0 && threadIdx.x < (n & 3)) x[n4 * 4 + threadIdx.x] *= s;
 }
 
+// grad[b, a, y, x, k] *= (k < 4 ? *g_box : k == 4 ? *g_conf : *g_cls), in place through the level's strides: the chain rule of a loss
+// whose three parts write disjoint channel groups of one stored gradient.  Every block leaves at once when all three scalars are exactly 1.
+// k_inner: the channel is the innermost loop (NHWC-backed heads, sk == 1), else x is (NCHW): neighbouring threads, neighbouring addresses.
+__global__ __launch_bounds__(256) void scale_head_groups_kernel(const Level lv, const float* __restrict__ g_box, const float* __restrict__ g_cls,
+                                                                const float* __restrict__ g_conf, int k_inner) {
+    const float sb = *g_box, sc = *g_cls, sf = *g_conf;
+    if (sb == 1.f && sc == 1.f && sf == 1.f) return;
+    const int64_t n = (int64_t)lv.B * lv.A * lv.H * lv.W * lv.K;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        int64_t r = i;
+        int k, x, y, a;
+        if (k_inner) {
+            k = (int)(r % lv.K); r /= lv.K;
+            x = (int)(r % lv.W); r /= lv.W;
+            y = (int)(r % lv.H); r /= lv.H;
+            a = (int)(r % lv.A); r /= lv.A;
+        } else {
+            x = (int)(r % lv.W); r /= lv.W;
+            y = (int)(r % lv.H); r /= lv.H;
+            k = (int)(r % lv.K); r /= lv.K;
+            a = (int)(r % lv.A); r /= lv.A;
+        }
+        const int64_t off = r * lv.sb + a * lv.sa + y * lv.sy + x * lv.sx + k * lv.sk;
+        lv.grad[off] *= k < 4 ? sb : (k == 4 ? sf : sc);
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -856,6 +960,61 @@ int fva_demo_loss(const float* targets, int32_t T, const fva_head_level* levels,
             FVA_LAUNCH_CHECK("demo_conf_kernel");
         }
     }
+    return FVA_OK;
+}
+
+int64_t fva_demo_ciou_loss_workspace(int32_t T, const fva_head_level* levels, int32_t nlevels) {
+    return fva_demo_loss_workspace(T, levels, nlevels);
+}
+
+int fva_demo_ciou_loss(const float* targets, int32_t T, const fva_head_level* levels, int32_t nlevels, float* loss_out, void* workspace,
+                       int64_t workspace_bytes, void* stream) {
+    if (!levels || nlevels < 1 || nlevels > 4 || !loss_out || !workspace || !targets || T < 1)
+        return fva_fail(FVA_ERR_ARG, "fva_demo_ciou_loss: bad argument (the reference needs >= 1 target)");
+    for (int l = 0; l < nlevels; ++l) {  // every level is checked before the first device call
+        int rc = check_level(levels[l], "fva_demo_ciou_loss");
+        if (rc) return rc;
+    }
+    if (workspace_bytes < fva_demo_ciou_loss_workspace(T, levels, nlevels)) return fva_fail(FVA_ERR_WORKSPACE, "fva_demo_ciou_loss: workspace too small");
+    hipStream_t s = (hipStream_t)stream;
+    Carver c{(char*)workspace};
+    double* acc = c.take<double>(8);
+    if (hipMemsetAsync(acc, 0, 64, s) != hipSuccess) return fva_fail(FVA_ERR_LAUNCH, "fva_demo_ciou_loss: memset failed");
+    for (int l = 0; l < nlevels; ++l) {
+        const Level lv = to_level(levels[l]);
+        const DemoBuf db = carve_demo(c, T, levels[l]);
+        const int64_t n = (int64_t)lv.B * lv.H * lv.W * lv.A;
+        const int blocks = (int)((n + 255) / 256 < CONF_BLOCKS ? (n + 255) / 256 : CONF_BLOCKS);
+        hipLaunchKernelGGL(demo_group_kernel, dim3(1), dim3(256), 2 * lv.B * 4, s, targets, T, lv.B, db.img_start, db.img_count, db.perm);
+        FVA_LAUNCH_CHECK("demo_group_kernel");
+        hipLaunchKernelGGL(demo_mask_kernel, dim3(blocks), dim3(256), 0, s, targets, lv, db);
+        FVA_LAUNCH_CHECK("demo_mask_kernel");
+        hipLaunchKernelGGL(ship_target_kernel, dim3(cdiv(T, 4) < 2048 ? cdiv(T, 4) : 2048), dim3(256), 0, s, targets, T, lv, db);
+        FVA_LAUNCH_CHECK("ship_target_kernel");
+        hipLaunchKernelGGL(demo_positive_kernel, dim3(cdiv(T, 256)), dim3(256), 0, s, T, db);
+        FVA_LAUNCH_CHECK("demo_positive_kernel");
+        hipLaunchKernelGGL(demo_conf_kernel, dim3(blocks), dim3(256), 0, s, lv, db, 0);
+        FVA_LAUNCH_CHECK("demo_conf_kernel");
+        hipLaunchKernelGGL(ship_level_final_kernel, dim3(1), dim3(256), 0, s, db, T, lv.K - 5, blocks, acc, loss_out, l == nlevels - 1 ? 1 : 0);
+        FVA_LAUNCH_CHECK("ship_level_final_kernel");
+        if (lv.grad) {
+            hipLaunchKernelGGL(demo_conf_kernel, dim3(blocks), dim3(256), 0, s, lv, db, 1);
+            FVA_LAUNCH_CHECK("demo_conf_kernel");
+        }
+    }
+    return FVA_OK;
+}
+
+int fva_scale_head_groups(const fva_head_level* level, const float* g_box, const float* g_cls, const float* g_conf, void* stream) {
+    if (!level || !level->grad || !g_box || !g_cls || !g_conf) return fva_fail(FVA_ERR_ARG, "fva_scale_head_groups: null pointer");
+    int rc = check_level(*level, "fva_scale_head_groups");
+    if (rc) return rc;
+    const Level lv = to_level(*level);
+    const int64_t n = (int64_t)lv.B * lv.A * lv.H * lv.W * lv.K;
+    int64_t g = (n + 255) / 256;
+    if (g > 2048) g = 2048;
+    hipLaunchKernelGGL(scale_head_groups_kernel, dim3((int)g), dim3(256), 0, (hipStream_t)stream, lv, g_box, g_cls, g_conf, lv.sk == 1 ? 1 : 0);
+    FVA_LAUNCH_CHECK("scale_head_groups_kernel");
     return FVA_OK;
 }
 

@@ -548,6 +548,12 @@ def conv_block_fwd(x, x_ptr, x_pad, weight, gamma, beta, bn, training, stride, d
     return z, s
 
 
+def _in_place_scalar(gout, g):
+    """The in-place conditions of scale_loss_grads for one upstream scalar and one gradient buffer of this package."""
+    return (gout.numel() == 1 and gout.dtype == torch.float32 and gout.is_cuda and g.is_cuda and g.dtype == torch.float32 and not gout.requires_grad
+            and g.storage_offset() == 0 and g.untyped_storage().nbytes() == g.numel() * 4 and g.data_ptr() % 16 == 0)
+
+
 def scale_loss_grads(ctx, gout):
     """Chain rule of the fused losses (loss.Yolov3Loss, the demo's ComputeLoss): their forward pass already filled ctx.grads with
     d loss / d head; backward multiplies by the upstream scalar.  For fp32 buffers that this package allocated the multiply runs IN
@@ -561,11 +567,45 @@ def scale_loss_grads(ctx, gout):
         if g is None:
             res.append(None)
             continue
-        if (gout.numel() == 1 and gout.dtype == torch.float32 and gout.is_cuda and g.is_cuda and g.dtype == torch.float32 and not gout.requires_grad
-                and g.storage_offset() == 0 and g.untyped_storage().nbytes() == g.numel() * 4 and g.data_ptr() % 16 == 0):
+        if _in_place_scalar(gout, g):
             _lib.call('fva_scale_by_device_scalar', _p(g), g.numel(), _p(gout), _stream())
         else:
             g = g * gout
+        res.append(g if g.dtype == dt else g.to(dt))
+    return res
+
+
+def scale_head_group_grads(ctx, g_box, g_cls, g_conf):
+    """Chain rule of a fused loss with three separately differentiable parts (the ship demo's ComputeLoss): ctx.grads holds, per level,
+    d (box + cls + conf) / d head [B, A * K, H, W], whose channel groups k < 4 / k == 4 / k >= 5 belong to the box / objectness / class
+    part alone; ctx.anchors_per_level the A of each level.  In place through ``fva_scale_head_groups`` (no traffic when all three
+    upstream scalars are exactly 1) under the conditions of scale_loss_grads, else a plain multiply per channel group."""
+    grads, ctx.grads = ctx.grads, None
+    if grads is None:
+        raise _released('the loss')
+    res = []
+    for g, dt, A in zip(grads, ctx.dtypes, ctx.anchors_per_level):
+        if g is None:
+            res.append(None)
+            continue
+        B, ch, H, W = g.shape
+        K = ch // A
+        if all(_in_place_scalar(s, g) for s in (g_box, g_cls, g_conf)):
+            sb, sc, sy, sx = g.stride()
+            lv = _lib.HeadLevel()
+            lv.data = lv.grad = g.data_ptr()
+            lv.sb, lv.sa, lv.sy, lv.sx, lv.sk = sb, K * sc, sy, sx, sc
+            lv.B, lv.A, lv.H, lv.W, lv.K = B, A, H, W, K
+            lv.stride = 1.0
+            _lib.call('fva_scale_head_groups', C.byref(lv), _p(g_box), _p(g_cls), _p(g_conf), _stream())
+        else:
+            g5 = g.unflatten(1, (A, K))
+            out = torch.empty_like(g)
+            o5 = out.unflatten(1, (A, K))
+            o5[:, :, 0:4] = g5[:, :, 0:4] * g_box
+            o5[:, :, 4:5] = g5[:, :, 4:5] * g_conf
+            o5[:, :, 5:] = g5[:, :, 5:] * g_cls
+            g = out
         res.append(g if g.dtype == dt else g.to(dt))
     return res
 

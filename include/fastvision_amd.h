@@ -407,6 +407,20 @@ int fva_demo_loss(const float* targets, int32_t T, const fva_head_level* levels,
                   void* workspace, int64_t workspace_bytes, void* stream);
 int64_t fva_demo_loss_workspace(int32_t T, const fva_head_level* levels, int32_t nlevels);
 
+/* Loss of the second demo (demos/yolov3_huaweiShip/utils/lossv3.py:35-120): the same assignment, ignore mask and masked objectness BCE;
+ * the box term is mean over T of 1 - CIoU(pred, target; 'xywh', eps 1e-7), pred = (sigmoid(z_xy) + cell, exp(z_wh) * anchor), with the
+ * demo's CIoU (fva_iou_pairwise kind 3, variant 1); class term BCE-with-logits, mean over T * C.  Arguments and argument rules as
+ * fva_demo_loss.  loss_out[4] = {box + cls + conf, box, cls, conf}; level.grad receives d (box + cls + conf) / d head: the box part in
+ * channels 0..3 of the matched (cell, anchor), the objectness part in channel 4, the class part in channels 5.. */
+int fva_demo_ciou_loss(const float* targets, int32_t T, const fva_head_level* levels, int32_t nlevels, float* loss_out,
+                       void* workspace, int64_t workspace_bytes, void* stream);
+int64_t fva_demo_ciou_loss_workspace(int32_t T, const fva_head_level* levels, int32_t nlevels);
+
+/* level->grad[b, a, y, x, k] *= (k < 4 ? *g_box : k == 4 ? *g_conf : *g_cls), in place through the level's strides; the three scalars
+ * are device memory and are not read on the host.  The chain rule of fva_demo_ciou_loss, whose three parts are separately
+ * differentiable but write disjoint channel groups of ONE stored gradient.  No memory traffic when all three are exactly 1. */
+int fva_scale_head_groups(const fva_head_level* level, const float* g_box, const float* g_cls, const float* g_conf, void* stream);
+
 /* IoU family on device (detection/tools/IOU.py, BOX.py).  kind: 0 IoU 1 GIoU 2 DIoU 3 CIoU;
  * mode: 0 xyxy 1 xywh 2 wh; variant: 0 library 1 demo (iou.py centre sums / minus sign).
  * pairwise: out[N] and (optional) grad_a[N][4 or 2] = d out / d a in the caller's box parametrisation (ties
@@ -430,7 +444,9 @@ typedef struct {
  * variant 1 -- postProcess (demos/yolov3_u/inference.py:58-88): rows ordered (y, x, a);
  *   xy = (2 sigmoid(t) - 0.5 + cell) * stride, wh = (2 sigmoid(t))^2 * anchor * stride (FEATURE anchors).
  *   With lb != NULL rows additionally go through :90-106: un-letterbox, clamp, xywh -> clamped xyxy in columns 0..3;
- *   rows the reference drops (w or h <= min_wh) keep their place with objectness -1. */
+ *   rows the reference drops (w or h <= min_wh) keep their place with objectness -1.
+ * variant 2 -- postProcess of the second demo (demos/yolov3_huaweiShip/inference.py:107-136): rows ordered (y, x, a);
+ *   xy = (sigmoid(t) + cell) * stride, wh = exp(t) * anchor * stride (FEATURE anchors); lb != NULL as for variant 1. */
 int fva_yolo_decode(const fva_head_level* levels, int32_t nlevels, int32_t variant, const fva_letterbox* lb,
                     float* out, int64_t rows_per_image, void* stream);
 
