@@ -151,6 +151,7 @@ PROTOTYPES = {
     'fva_scale_head_groups': (_I, [_H, _P, _P, _P, _P]),
     'fva_iou_pairwise': (_I, [_I, _I, _I, _P, _P, _P, _P, _L, _F, _P]),
     'fva_iou_batch': (_I, [_I, _I, _I, _P, _P, _P, _L, _L, _F, _P]),
+    'fva_map_match': (_I, [_P, _P, _I, _I, _P, _I, C.POINTER(C.c_double), _I, _F, _P, _P, _P]),
     'fva_adam_step': (_I, [_P, _P, _I, _L, _F, _F, _F, _F, _F, _L, _F, _P]),
     'fva_adam_step_dev': (_I, [_P, _P, _I, _L, _P, _F, _F, _F, _F, _P, _F, _P]),
     'fva_gather_cast': (_I, [_P, _I, _L, _P, _I, _P]),

@@ -668,6 +668,94 @@ __global__ void iou_batch_kernel(int kind, int mode, int variant, const float* a
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// Validation mAP: predictions against targets for a whole batch (metrics/map.py:17-83 of the reference, whose argsort and two
+// np.unique calls reduce to two arg-reductions).  One block per image; nothing is shared between blocks.
+//   1. every prediction p picks, among the targets t of its image with class[t] == class[p] and IoU(t, p) > (float)thr[0], the one
+//      with the highest IoU (equal IoU: the lowest t);
+//   2. every target goes to the LOWEST-indexed prediction that picked it (the reference does not sort again between its two unique
+//      calls); a prediction that loses gets nothing, whatever else it would have matched;
+//   3. bit k of a winner's flag word is (double)IoU > thr[k].
+// The IoU is iou_batch_kernel's (kind 0, xyxy, target first): the same expression in the same translation unit, hence the same bits.
+// winner [T]: the workspace; each block initialises and reads only the entries of its own image's targets.  Its accesses are agent-scope
+// atomics, so that the winners written by one wave are what another wave of the block reads after the barrier, whatever the vector L1 holds.
+constexpr int MAP_THREADS = 256;
+constexpr int MAP_NO_WINNER = 0x7fffffff;
+struct MapThr {
+    double v[16];
+    int n;
+};
+__global__ __launch_bounds__(MAP_THREADS) void map_match_kernel(const float* __restrict__ det, const int32_t* __restrict__ kept, int max_det,
+                                                                const float* __restrict__ tg, int T, const MapThr thr, float eps,
+                                                                int32_t* winner, uint16_t* __restrict__ flags) {
+    __shared__ float s_row[MAP_THREADS][5];   // class, x1, y1, x2, y2 of the image's targets in the current chunk of 256 rows
+    __shared__ int s_t[MAP_THREADS];
+    __shared__ int s_n;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const float fb = (float)b;                // the image index compares as a float, like labels[:, 0] == img_idx
+    int P = kept[b];
+    P = P < 0 ? 0 : (P > max_det ? max_det : P);
+    const float* dimg = det + (size_t)b * max_det * 6;
+    uint16_t* fimg = flags + (size_t)b * max_det;
+    const float thr0 = (float)thr.v[0];
+
+    for (int p = tid; p < max_det; p += MAP_THREADS) fimg[p] = 0;   // padded rows included; rows >= P are not read anywhere
+    for (int t = tid; t < T; t += MAP_THREADS)
+        if (tg[(size_t)t * 6] == fb) __hip_atomic_store(&winner[t], MAP_NO_WINNER, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __syncthreads();
+
+    // step 1, in tiles of 256 predictions x chunks of 256 target rows
+    for (int p0 = 0; p0 < P; p0 += MAP_THREADS) {
+        const int p = p0 + tid;
+        const bool active = p < P;
+        float pb[4] = {0.f, 0.f, 0.f, 0.f}, pcls = 0.f;
+        if (active) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) pb[i] = dimg[(size_t)p * 6 + i];
+            pcls = dimg[(size_t)p * 6 + 5];
+        }
+        int best_t = -1;
+        float best_iou = 0.f;
+        for (int c0 = 0; c0 < T; c0 += MAP_THREADS) {
+            if (tid == 0) s_n = 0;
+            __syncthreads();
+            const int t = c0 + tid;
+            if (t < T && tg[(size_t)t * 6] == fb) {
+                const int k = atomicAdd(&s_n, 1);   // any order: the tie rule below names the target index itself
+                s_t[k] = t;
+#pragma unroll
+                for (int i = 0; i < 5; ++i) s_row[k][i] = tg[(size_t)t * 6 + 1 + i];
+            }
+            __syncthreads();
+            const int n = s_n;
+            if (active) {
+                for (int k = 0; k < n; ++k) {
+                    if (!(s_row[k][0] == pcls)) continue;
+                    const float iou = iou_plain_d(load_box(&s_row[k][1], 0, true), load_box(pb, 0, false), eps).v;
+                    if (!(iou > thr0)) continue;
+                    const int tk = s_t[k];
+                    if (best_t < 0 || iou > best_iou || (iou == best_iou && tk < best_t)) { best_iou = iou; best_t = tk; }
+                }
+            }
+            __syncthreads();                        // the chunk is read before the next one overwrites it
+        }
+        if (best_t >= 0) atomicMin(&winner[best_t], p);
+    }
+    __syncthreads();
+
+    // steps 2 and 3: a prediction picked one target, so it wins at most one, and no two threads write the same flag word
+    for (int t = tid; t < T; t += MAP_THREADS) {
+        if (!(tg[(size_t)t * 6] == fb)) continue;
+        const int w = __hip_atomic_load(&winner[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (w < 0 || w >= P) continue;
+        const double iou = (double)iou_plain_d(load_box(tg + (size_t)t * 6 + 2, 0, true), load_box(dimg + (size_t)w * 6, 0, false), eps).v;
+        unsigned bits = 0;
+#pragma unroll
+        for (int k = 0; k < 16; ++k) bits |= (k < thr.n && iou > thr.v[k] ? 1u : 0u) << k;   // unrolled: thr stays in the kernel arguments
+        fimg[w] = (uint16_t)bits;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // Stand-alone BiCrossEntropyLoss (loss/classification_loss.py:36-65): per element
 //   l = -t log(p + 1e-8) - (1 - t) log(1 - p + 1e-8),  p = y or sigmoid(y),  t = one-hot(label) or the dense target,
 // times an optional per-element weight; block partial sums in fixed order, and dl/dy for the backward.
@@ -1082,6 +1170,21 @@ int fva_iou_batch(int kind, int mode, int variant, const float* a, const float* 
     hipLaunchKernelGGL(iou_batch_kernel, dim3((int)((N * M + 255) / 256 < 2048 ? (N * M + 255) / 256 : 2048)), dim3(256), 0,
                        (hipStream_t)stream, kind, mode, variant, a, b, out, N, M, eps);
     FVA_LAUNCH_CHECK("iou_batch_kernel");
+    return FVA_OK;
+}
+
+int fva_map_match(const float* det, const int32_t* kept, int32_t B, int32_t max_det, const float* targets, int32_t T, const double* thr,
+                  int32_t n_thr, float eps, int32_t* workspace, uint16_t* flags, void* stream) {
+    if (!det || !kept || !thr || !flags) return fva_fail(FVA_ERR_ARG, "fva_map_match: null pointer");
+    if (B <= 0 || max_det <= 0 || T < 0) return fva_fail(FVA_ERR_ARG, "fva_map_match: bad shape (B %d, max_det %d, T %d)", B, max_det, T);
+    if (n_thr < 1 || n_thr > 16) return fva_fail(FVA_ERR_ARG, "fva_map_match: n_thr %d outside 1..16", n_thr);
+    if (T > 0 && (!targets || !workspace)) return fva_fail(FVA_ERR_ARG, "fva_map_match: null targets or workspace with T %d", T);
+    MapThr mt;
+    for (int k = 0; k < 16; ++k) mt.v[k] = k < n_thr ? thr[k] : 0.0;
+    mt.n = n_thr;
+    hipLaunchKernelGGL(map_match_kernel, dim3(B), dim3(MAP_THREADS), 0, (hipStream_t)stream, det, kept, max_det, targets, T, mt, eps, workspace,
+                       flags);
+    FVA_LAUNCH_CHECK("map_match_kernel");
     return FVA_OK;
 }
 

@@ -5,9 +5,14 @@ a true positive; ``fetch()`` integrates precision over recall per class (101-poi
 (mAP per threshold, the classes seen, AP per class and threshold).
 
 Host-side evaluation utility (numpy); the pairwise IoU matrix comes from the device kernel (fva_iou_batch) when the boxes live on
-the GPU.  The demo's fit loop receives this object but never calls it (cfg/_fit.py:6); inference.py does."""
+the GPU.  The demo's fit loop receives this object but never calls it (cfg/_fit.py:6); inference.py does.
+
+``process_batch(dets, kept, targets)`` matches a whole NMS batch in one launch without a host read-back (metrics/map.py has it);
+``fetch()`` builds the rows ``process_one`` would have appended."""
 import numpy as np
 import torch
+
+from ....metrics.map import BatchMatching
 
 __all__ = ['mean_average_precision']
 
@@ -27,7 +32,7 @@ def _iou_matrix(a, b):
     return inter / (area_a[:, None] + area_b[None, :] - inter + 1e-7)
 
 
-class mean_average_precision:
+class mean_average_precision(BatchMatching):
     def __init__(self, map_iou_values):
         self.map_iou_values = np.asarray(map_iou_values, dtype=np.float64)
         self.correct_all_images = []
@@ -68,6 +73,7 @@ class mean_average_precision:
 
     def fetch(self):
         nt = len(self.map_iou_values)
+        self.materialize()
         if not self.correct_all_images:
             return np.zeros(nt), np.array([0]), [0]
         correct = np.concatenate(self.correct_all_images, axis=0)

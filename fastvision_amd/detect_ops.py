@@ -11,7 +11,7 @@ import torch
 from . import _lib
 from .ops import _p, _stream, require_gpu
 
-__all__ = ['yolo_decode', 'nms_batch', 'NMS_LIBRARY', 'NMS_DEMO', 'NMS_DEMO_BATCH']
+__all__ = ['yolo_decode', 'nms_batch', 'nms_batch_padded', 'NMS_LIBRARY', 'NMS_DEMO', 'NMS_DEMO_BATCH']
 
 # (box_mode, score_mode, rethreshold, class_gap, max_nms) of the three reference wrappers
 NMS_LIBRARY = dict(box_mode=0, score_mode=0, rethreshold=0, class_gap=0.0, max_nms=0)        # detection/tools/NMS.py
@@ -51,11 +51,9 @@ def yolo_decode(heads, anchors, strides, variant=0, letterbox=None):
     return out
 
 
-def nms_batch(pred, conf_thres, iou_thres, max_det, mode):
-    """pred [B,R,K] fp32 CUDA (decoded rows).  Returns per image (det [n,6] = x1,y1,x2,y2,score,category; rows [n] =
-    source row of each detection), highest score first.  Two host read-backs per call (candidate counts, kept counts):
-    the reference's boolean-mask indexing synchronises at the same two points per IMAGE."""
-    require_gpu(pred, 'nms_batch')
+def _nms_padded(pred, conf_thres, iou_thres, max_det, mode, who):
+    """The launches behind nms_batch / nms_batch_padded: (out, rows, kept, nmax), nmax = the largest candidate count of the batch."""
+    require_gpu(pred, who)
     assert pred.dim() == 3 and pred.dtype == torch.float32
     pred = pred.contiguous()
     B, R, K = pred.shape
@@ -69,11 +67,10 @@ def nms_batch(pred, conf_thres, iou_thres, max_det, mode):
     _lib.call('fva_nms_candidates', _p(pred), B, R, K, C.byref(prm), _p(cand), cb, _p(counts), _stream())
     counts_h = counts.cpu()
     nmax = int(counts_h.max())
-    empty = (torch.zeros(0, 6, device=dev), torch.zeros(0, dtype=torch.int64, device=dev))
-    if nmax == 0:
-        return [empty] * B
     out = torch.empty(B, max_det, 6, dtype=torch.float32, device=dev)
     rows = torch.empty(B, max_det, dtype=torch.int32, device=dev)
+    if nmax == 0:
+        return out, rows, torch.zeros(B, dtype=torch.int32, device=dev), 0
     kept = torch.empty(B, dtype=torch.int32, device=dev)
     wb = lib.fva_nms_select_workspace(B, nmax)
     if wb <= MASK_BYTES_PER_CALL or B == 1:
@@ -95,5 +92,25 @@ def nms_batch(pred, conf_thres, iou_thres, max_det, mode):
             ws = torch.empty(wb1, dtype=torch.uint8, device=dev)
             _lib.call('fva_nms_select', _p(cand1), _p(cnt1), 1, R, n_b, C.byref(prm), _p(ws), wb1, _p(out[b]), _p(rows[b]),
                       _p(kept[b:b + 1]), _stream())
+    return out, rows, kept, nmax
+
+
+def nms_batch_padded(pred, conf_thres, iou_thres, max_det, mode):
+    """pred [B,R,K] fp32 CUDA (decoded rows).  Returns (out [B,max_det,6] fp32 = x1,y1,x2,y2,score,category, highest score first;
+    rows [B,max_det] int32 = source row of each detection; kept [B] int32), all on the device: image b's detections are
+    out[b, :kept[b]], and what lies at or beyond kept[b] is uninitialised.  The same launches as nms_batch without its read-back of
+    ``kept``.  ONE host read-back per call remains: the candidate counts, which size the suppression workspace."""
+    return _nms_padded(pred, conf_thres, iou_thres, max_det, mode, 'nms_batch_padded')[:3]
+
+
+def nms_batch(pred, conf_thres, iou_thres, max_det, mode):
+    """pred [B,R,K] fp32 CUDA (decoded rows).  Returns per image (det [n,6] = x1,y1,x2,y2,score,category; rows [n] =
+    source row of each detection), highest score first.  Two host read-backs per call (candidate counts, kept counts):
+    the reference's boolean-mask indexing synchronises at the same two points per IMAGE.  nms_batch_padded plus the slicing."""
+    out, rows, kept, nmax = _nms_padded(pred, conf_thres, iou_thres, max_det, mode, 'nms_batch')
+    dev = pred.device
+    empty = (torch.zeros(0, 6, device=dev), torch.zeros(0, dtype=torch.int64, device=dev))
+    if nmax == 0:
+        return [empty] * pred.shape[0]
     kept_h = kept.cpu().tolist()
-    return [(out[b, :kept_h[b]], rows[b, :kept_h[b]].long()) if kept_h[b] else empty for b in range(B)]
+    return [(out[b, :kept_h[b]], rows[b, :kept_h[b]].long()) if kept_h[b] else empty for b in range(pred.shape[0])]

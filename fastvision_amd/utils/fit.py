@@ -3,12 +3,15 @@
 ``_train`` keeps the reference's per-batch contract (fit.py:52-66): pred = model(images); optimizer.zero_grad();
 loss = self.loss(pred, labels); loss.backward(); optimizer.step(); scheduler.step() per epoch.  ``_val`` follows
 fit.py:73-105: eval-mode forward with decode, validation loss, NMS (conf 0.25, IoU 0.45, 300 detections) and
-CalculateMAP over IoU 0.5:0.95 -- decode and NMS run in the HIP kernels, one NMS pass per batch instead of one per image.
+CalculateMAP over IoU 0.5:0.95 -- decode and NMS run in the HIP kernels, one NMS pass per batch instead of one per image, and the
+predictions of a batch are matched to its targets in one launch (CalculateMAP.process_batch): one host read-back per batch (the NMS
+candidate counts), the losses and the mAP rows are read back once at the end.
 """
 import numpy as np
 import torch
 
-from ..detection.tools import non_max_suppression_images, xywh2xyxy
+from ..detect_ops import NMS_LIBRARY, nms_batch_padded
+from ..detection.tools import xywh2xyxy
 from ..metrics import CalculateMAP
 from .checkpoints import SaveModel
 
@@ -106,20 +109,23 @@ class Fit:
         loader = self.val_loader or self.train_loader
         map_est = CalculateMAP(map_iou_values=np.linspace(0.5, 0.95, 10))
         self.model.eval()
-        losses = []
+        losses, scales = [], {}
         with torch.no_grad():
             for images, labels in loader:
                 images, labels = self._to_device(images, labels)
                 head_out, results = self.model(images, val=True)
-                losses.append(float(self.loss(head_out, labels)))
-                scale = torch.tensor([images.size(3), images.size(2), images.size(3), images.size(2)]).to(labels)
-                dets = non_max_suppression_images(results, conf_thres=0.25, iou_thres=0.45, max_det=300)
-                for img_idx, (conf, cls, xyxy) in enumerate(dets):
-                    predict = torch.cat([cls.float(), conf, xyxy], dim=1)
-                    target = labels[labels[:, 0] == img_idx, 1:].clone()
-                    target[:, 1:] = xywh2xyxy(target[:, 1:]) * scale
-                    map_est.process_one(predict, target)
-        out = {'loss': losses}
+                losses.append(self.loss(head_out, labels).detach())       # device tensor, read back once below (as in _train)
+                key = (images.size(3), images.size(2), labels.device, labels.dtype)
+                if key not in scales:                                      # one upload per image size, not one per batch
+                    scales[key] = torch.tensor([images.size(3), images.size(2), images.size(3), images.size(2)]).to(labels)
+                # the whole batch at once (GPU tensors; there is no CPU path): one NMS pass, whose candidate-count read-back is the batch's
+                # only host sync, the labels of all images converted together, one matching launch; the mAP rows are built on the host
+                # when the estimator is read below
+                dets, _, kept = nms_batch_padded(results, 0.25, 0.45, 300, NMS_LIBRARY)
+                targets = torch.cat([labels[:, :2], xywh2xyxy(labels[:, 2:6]) * scales[key]], dim=1)
+                map_est.process_batch(dets, kept, targets)
+        out = {'loss': torch.stack([l.reshape(()) for l in losses]).float().cpu().tolist() if losses else []}
+        map_est.materialize()
         if map_est.seen_all_targets_cls and map_est.correct_all_images:
             out['map_each_iou'], out['map_each_cls'], out['map_each_cls_idx'] = map_est.fetch()
         self.last_val = out

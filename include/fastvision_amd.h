@@ -474,6 +474,19 @@ int fva_nms_select(const void* cand, const int32_t* counts, int32_t B, int32_t R
                    void* workspace, int64_t workspace_bytes, float* out, int32_t* out_rows, int32_t* keep_counts,
                    void* stream);
 
+/* Validation mAP, the matching of metrics/map.py:17-83 for a whole batch in one launch and without a host read-back.
+ * det [B][max_det][6] = x1, y1, x2, y2, score, category and kept [B] (DEVICE int32) are fva_nms_select's out and keep_counts;
+ * targets [T][6] = image index, category, x1, y1, x2, y2 in pixels, in any order (rows whose image index is not one of 0..B-1 are
+ * ignored; T may be 0); thr [n_thr] is a HOST array of IoU thresholds, 1 <= n_thr <= 16, read before the call returns.
+ *   1. a prediction picks, among the targets of its image with an equal category (compared as floats) and IoU > (float)thr[0],
+ *      the one with the highest IoU -- the lowest target row when two are equal;
+ *   2. a target goes to the lowest-indexed prediction that picked it; every other prediction gets nothing;
+ *   3. bit k of flags [B][max_det] (uint16) is (double)IoU > thr[k] for a winner and 0 otherwise.
+ * The IoU has the bits of fva_iou_batch (kind 0, mode 0, eps) with the target as the first box.  Rows at or beyond kept[b] are
+ * never read and their flags are 0.  workspace: T int32, no initial value needed (may be NULL when T is 0). */
+int fva_map_match(const float* det, const int32_t* kept, int32_t B, int32_t max_det, const float* targets, int32_t T,
+                  const double* thr, int32_t n_thr, float eps, int32_t* workspace, uint16_t* flags, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Input side (scope row f-3): decoded uint8 RGB (HWC) images -> the [B][3][H][W] fp32 input batch in one launch.
  * A "paste job" resizes one source image with OpenCV's 8-bit INTER_LINEAR arithmetic (an exact 2x decimation is
