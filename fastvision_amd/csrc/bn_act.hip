@@ -3,7 +3,7 @@
 // contiguous (NHWC), no LDS except for the per-block channel reductions.
 //
 // Algorithmic bytes per element (bf16): apply = 2 (y) + 2 (z) [+2 residual]; backward pass 1 = 4 (dz, y);
-// backward pass 2 = 4 + 2 (dy).
+// backward pass 2 = 4 + 2 (dy); frozen statistics: ONE backward pass = 4 + 2.
 //
 // Replaces nn.BatchNorm2d / nn.SiLU / `identity + conv2` (reference classfication/models/darknet53.py:11-17,
 // 28-31, 58-62), Conv2d(bias) -> BatchNorm2d -> ReLU (classfication/models/vgg.py:39-48) and nn.Upsample + torch.cat
@@ -548,6 +548,163 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const T* __restrict__
     }
 }
 
+// Frozen statistics (the BatchNorm in eval mode, its convolution and affine parameters still training): scale and shift do not depend
+// on the batch, so dY = scale * dU needs no batch sum and the two backward passes above collapse into this one -- 4 (dz, y) + 2 (dY)
+// bytes per element in bf16 where reduce + apply move 10.  The row walk, the lane-constant channel chunk, the U loads in flight and the
+// zero border rows are those of bn_bwd_apply_kernel.  SUMS: the lane also keeps s1 = sum dU and s2 = sum dU * (y - m) * r of its channel
+// chunk in registers (m = the running mean, minus the convolution bias in the VGG block; r = 1 / sqrt(running_var + eps)); the block folds
+// them through LDS ([2][256 / cpp][C] floats, as bn_bwd_reduce_kernel) into ONE row of the [gridDim.x][2][C] table: fixed order, no
+// atomics.  Without SUMS (neither gamma nor beta asks for a gradient) nothing but dY is written.
+//
+// One element: dU and dY = scale * dU.  dY has no second term, so whatever dU loses shows in full.  ReLU: dU is dz or 0 and the product is
+// rounded once.  SiLU'(u) = s (1 + u (1 - s)) has a zero at u = -1.278 where the two terms cancel: there the 2^-24 of an fp32 sigmoid is
+// many ulps of the result (a CPU model of this arithmetic missed 32 x (e32 + 2^-24 |dY|) on 1 of 122 880 and 17 of 1.1 M elements).  fp32
+// tensors therefore evaluate it in double and round once, as ReLU's fp32 three-term sum above (the fp32 pass moves 12 B per element and
+// stays HBM-bound); bf16 tensors keep fp32 arithmetic -- half a bf16 ulp, 2^-9 of the result, is the error of the store.
+template <typename Act, typename T>
+__device__ __forceinline__ void frozen_elem(float dz, float y, float sc, float sh, float& du, float& dy) {
+    if constexpr (std::is_same<Act, ActSiLU>::value && std::is_same<T, float>::value) {
+        const double u = __builtin_fma((double)y, (double)sc, (double)sh);
+        const double s = 1.0 / (1.0 + exp(-u));
+        const double d = (double)dz * (s * (1.0 + u * (1.0 - s)));
+        du = (float)d;
+        dy = (float)((double)sc * d);
+    } else {
+        du = Act::du(dz, y, sc, sh);
+        dy = sc * du;
+    }
+}
+
+template <typename Act, typename T, bool SUMS>
+__global__ __launch_bounds__(256) void bn_frozen_bwd_kernel(const T* __restrict__ dz, const T* __restrict__ y,
+                                                            const float* __restrict__ scale, const float* __restrict__ shift,
+                                                            const float* __restrict__ m, const float* __restrict__ r,
+                                                            float* __restrict__ part, T* __restrict__ dy, const HaloIdx h, int nrows) {
+    constexpr int EPC = Vec16<T>::N, U = FVA_BN_UNROLL;
+    extern __shared__ float red[];             // SUMS: [2][rpi][C]
+    const int row_chunks = h.Wp * h.cpp;
+    const int cmask = h.cpp - 1, cshift = 31 - __builtin_clz(h.cpp);
+    const int cc = threadIdx.x & cmask;
+    float sc[EPC], sh[EPC], mu[EPC], rs[EPC], s1[EPC], s2[EPC];
+#pragma unroll
+    for (int e = 0; e < EPC; ++e) {
+        const int c = cc * EPC + e;
+        sc[e] = scale[c]; sh[e] = shift[c];
+        if constexpr (SUMS) { mu[e] = m[c]; rs[e] = r[c]; s1[e] = s2[e] = 0.f; }
+    }
+    Vec16<T> g[U], v[U];
+    bool ok[U];
+    int64_t m0 = 0;
+    auto set_row = [&](int row) -> bool {       // false: a border row
+        const int b = row / h.Hp, yy = row - b * h.Hp - h.pad;
+        m0 = ((int64_t)b * h.H + yy) * h.W;
+        return yy >= 0 && yy < h.H;
+    };
+    auto load = [&](int i0) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int i = i0 + u * 256;
+            const int xx = (i >> cshift) - h.pad;
+            ok[u] = i < row_chunks && xx >= 0 && xx < h.W;
+            const int64_t off = (m0 + (ok[u] ? xx : 0)) * h.C + cc * EPC;
+            g[u] = ld_last<T>(dz + off);
+            v[u] = ld_last<T>(y + off);
+        }
+    };
+    for (int row = blockIdx.x; row < nrows; row += gridDim.x) {
+        const bool row_in = set_row(row);
+        T* orow = dy + (int64_t)row * row_chunks * EPC;
+        if (!row_in) {
+            Vec16<T> zero;
+#pragma unroll
+            for (int e = 0; e < EPC; ++e) zero.set(e, 0.f);
+            for (int i = threadIdx.x; i < row_chunks; i += 256) *(Vec16<T>*)(orow + (int64_t)i * EPC) = zero;
+            continue;
+        }
+        for (int i0 = threadIdx.x; i0 < row_chunks; i0 += 256 * U) {
+            load(i0);
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int i = i0 + u * 256;
+                Vec16<T> out;
+#pragma unroll
+                for (int e = 0; e < EPC; ++e) {
+                    const float yv = v[u].get(e);
+                    float du, dyv;
+                    frozen_elem<Act, T>(g[u].get(e), yv, sc[e], sh[e], du, dyv);
+                    if (!ok[u]) du = dyv = 0.f;                                                 // a masked chunk adds nothing to the sums
+                    out.set(e, dyv);
+                    if constexpr (SUMS) {
+                        s1[e] += du;
+                        s2[e] += du * (yv - mu[e]) * rs[e];
+                    }
+                }
+                if (i < row_chunks) *(Vec16<T>*)(orow + (int64_t)i * EPC) = out;
+            }
+        }
+    }
+    if constexpr (SUMS) {
+        const int rpi = 256 >> cshift, py = threadIdx.x >> cshift;
+#pragma unroll
+        for (int e = 0; e < EPC; ++e) {
+            red[(0 * rpi + py) * h.C + cc * EPC + e] = s1[e];
+            red[(1 * rpi + py) * h.C + cc * EPC + e] = s2[e];
+        }
+        __syncthreads();
+        for (int i = threadIdx.x; i < 2 * h.C; i += 256) {
+            const int which = i >= h.C, c = i - which * h.C;
+            float s = 0.f;
+            for (int k = 0; k < rpi; ++k) s += red[(which * rpi + k) * h.C + c];
+            part[((int64_t)blockIdx.x * 2 + which) * h.C + c] = s;
+        }
+    }
+}
+
+// the table of bn_frozen_bwd_kernel -> dbeta = s1, dgamma = s2 and, for a convolution bias in front of the BatchNorm (which no longer
+// cancels with fixed statistics), dbias = scale * s1.  The two-level fold of the other finalize kernels; no coefficient table.
+__global__ __launch_bounds__(1024) void bn_frozen_bwd_finalize_kernel(const float* __restrict__ part, int nblocks, int C,
+                                                                      const float* __restrict__ scale, float* dgamma, float* dbeta, float* dbias,
+                                                                      const double* __restrict__ pre, int pre_rows) {
+    __shared__ double red[2][FIN_G][17];
+    const int cx = threadIdx.x & 15, ry = threadIdx.x >> 4;
+    const int c = blockIdx.x * 16 + cx;
+    double s1 = 0.0, s2 = 0.0;
+    if (c < C) {
+        if (pre_rows > 0) {
+            for (int r = ry; r < pre_rows; r += FIN_G) {
+                s1 += pre[((int64_t)r * 2 + 0) * C + c];
+                s2 += pre[((int64_t)r * 2 + 1) * C + c];
+            }
+        } else {
+            reduce_partials(part, nblocks, C, c, ry, s1, s2);
+        }
+    }
+    red[0][ry][cx] = s1;
+    red[1][ry][cx] = s2;
+    __syncthreads();
+    if (ry == 0 && c < C) {
+        s1 = s2 = 0.0;
+#pragma unroll 8                                 // (fully unrolled, the 128 LDS doubles in flight spill at 1024 threads per block)
+        for (int k = 0; k < FIN_G; ++k) {
+            s1 += red[0][k][cx];
+            s2 += red[1][k][cx];
+        }
+        if (dbeta) dbeta[c] = (float)s1;
+        if (dgamma) dgamma[c] = (float)s2;
+        if (dbias) dbias[c] = (float)((double)scale[c] * s1);
+    }
+}
+
+// m = running_mean (- bias), r = 1 / sqrt(running_var + eps): the divisor of bn_eval_coeffs_kernel, so that scale == gamma * r up to one rounding
+__global__ void bn_frozen_stats_kernel(int C, const float* __restrict__ rm, const float* __restrict__ rv, const float* __restrict__ bias, float eps,
+                                       float* m, float* r) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c < C) {
+        m[c] = bias ? rm[c] - bias[c] : rm[c];
+        r[c] = 1.0f / sqrtf(rv[c] + eps);
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------------
 // nearest x2 upsample + channel concat into a halo buffer (pad 1)
 template <typename T>
@@ -783,9 +940,89 @@ int bwd_apply_impl(const char* who, int dtype, const void* dz, const void* y, co
     return FVA_OK;
 }
 
+// The grid of the frozen pass: blocks walk the padded rows, at most FROZEN_GRID of them (256 CUs x 4 resident blocks of 4 waves at the
+// register count of the bf16 form) -- and at most one per 64 pixels, so that the partial table (2 C floats per block, written once and read
+// once: 16 C bytes) stays under 16 / (64 * 6) = 4.2 % of the pass's own 6 M C bytes (bf16).
+constexpr int FROZEN_GRID = 1024;
+int frozen_grid(const HaloIdx& h) {
+    const int64_t nrows = (int64_t)h.B * h.Hp, by_pixels = (int64_t)h.B * h.H * h.W / 64;
+    int64_t g = nrows < FROZEN_GRID ? nrows : FROZEN_GRID;
+    if (g > by_pixels) g = by_pixels;
+    return g < 1 ? 1 : (int)g;
+}
+
+template <typename Act>
+int frozen_bwd_impl(const char* who, int dtype, const void* dz, const void* y, const float* scale, const float* shift, const float* m,
+                    const float* r, float* partial, void* dy, int dy_pad, int B, int H, int W, int C, void* stream) {
+    int rc = check_chan(dtype, C, who);
+    if (rc) return rc;
+    if (!dz || !y || !scale || !shift || !dy || (partial && (!m || !r))) return fva_fail(FVA_ERR_ARG, "%s: null pointer", who);
+    HaloIdx h;
+    if ((rc = checked_halo(who, dtype, B, H, W, C, dy_pad, true, h))) return rc;
+    // without sums there is no table to keep small: one block per padded row up to ACC_GRID, as the apply passes (at frozen_grid()'s 200
+    // blocks the 32 x 20 x 20 x 1024 map took 48 us where the pass with sums and its fold took 37; one block per row: 20 us)
+    const int nrows = B * h.Hp, grid = partial ? frozen_grid(h) : (nrows < ACC_GRID ? nrows : ACC_GRID);
+    by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        if (partial)
+            hipLaunchKernelGGL((bn_frozen_bwd_kernel<Act, T, true>), dim3(grid), dim3(256), 2 * 256 * Vec16<T>::N * 4, (hipStream_t)stream, (const T*)dz,
+                               (const T*)y, scale, shift, m, r, partial, (T*)dy, h, nrows);
+        else
+            hipLaunchKernelGGL((bn_frozen_bwd_kernel<Act, T, false>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (const T*)dz, (const T*)y, scale,
+                               shift, m, r, partial, (T*)dy, h, nrows);
+    });
+    FVA_LAUNCH_CHECK("bn_frozen_bwd_kernel");
+    return FVA_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int32_t fva_bn_frozen_bwd_blocks(int dtype, int B, int H, int W, int C, int dy_pad) {
+    HaloIdx h;
+    if (check_chan(dtype, C, "fva_bn_frozen_bwd_blocks") || checked_halo("fva_bn_frozen_bwd_blocks", dtype, B, H, W, C, dy_pad, true, h)) return 0;
+    return frozen_grid(h);
+}
+
+int fva_bn_silu_frozen_bwd(int dtype, const void* dz, const void* y, const float* scale, const float* shift, const float* m, const float* r,
+                           float* partial, void* dy, int dy_pad, int B, int H, int W, int C, void* stream) {
+    return frozen_bwd_impl<ActSiLU>("fva_bn_silu_frozen_bwd", dtype, dz, y, scale, shift, m, r, partial, dy, dy_pad, B, H, W, C, stream);
+}
+
+int fva_bn_relu_frozen_bwd(int dtype, const void* dz, const void* y, const float* scale, const float* shift, const float* m, const float* r,
+                           float* partial, void* dy, int dy_pad, int B, int H, int W, int C, void* stream) {
+    return frozen_bwd_impl<ActReLU>("fva_bn_relu_frozen_bwd", dtype, dz, y, scale, shift, m, r, partial, dy, dy_pad, B, H, W, C, stream);
+}
+
+int fva_bn_frozen_bwd_finalize(float* partial, int32_t nblocks, int32_t partial_rows, int C, const float* scale, float* dgamma, float* dbeta,
+                               float* dbias, void* stream) {
+    if (!partial || (!dgamma && !dbeta && !dbias) || (dbias && !scale) || nblocks <= 0 || C <= 0)
+        return fva_fail(FVA_ERR_ARG, "fva_bn_frozen_bwd_finalize: bad argument");
+    if (partial_rows < fva_bn_partial_rows(nblocks))
+        return fva_fail(FVA_ERR_WORKSPACE, "fva_bn_frozen_bwd_finalize: the table holds %d rows, %d rows of producers need fva_bn_partial_rows() = %d",
+                        partial_rows, nblocks, fva_bn_partial_rows(nblocks));
+    const double* pre = nullptr;
+    int pre_rows = 0;
+    if (nblocks >= PRE_MIN) {
+        pre_rows = cdiv(nblocks, PRE_ROWS);
+        double* tail = (double*)(partial + ((int64_t)nblocks * 2 * C + 1) / 2 * 2);
+        pre = tail;
+        hipLaunchKernelGGL(bn_prereduce_kernel, dim3(cdiv(C, 16), pre_rows), dim3(1024), 0, (hipStream_t)stream, partial, nblocks, C, tail);
+        FVA_LAUNCH_CHECK("bn_prereduce_kernel");
+    }
+    hipLaunchKernelGGL(bn_frozen_bwd_finalize_kernel, dim3(cdiv(C, 16)), dim3(1024), 0, (hipStream_t)stream, partial, nblocks, C, scale, dgamma,
+                       dbeta, dbias, pre, pre_rows);
+    FVA_LAUNCH_CHECK("bn_frozen_bwd_finalize_kernel");
+    return FVA_OK;
+}
+
+int fva_bn_frozen_stats(int32_t C, const float* rm, const float* rv, const float* bias, float eps, float* m, float* r, void* stream) {
+    if (!rm || !rv || !m || !r || C <= 0) return fva_fail(FVA_ERR_ARG, "fva_bn_frozen_stats: bad argument");
+    hipLaunchKernelGGL(bn_frozen_stats_kernel, dim3(cdiv(C, 256)), dim3(256), 0, (hipStream_t)stream, C, rm, rv, bias, eps, m, r);
+    FVA_LAUNCH_CHECK("bn_frozen_stats_kernel");
+    return FVA_OK;
+}
 
 int fva_bn_finalize(float* part, int32_t nblocks, int32_t partial_rows, int64_t count, int32_t C, const float* gamma, const float* beta,
                     float* running_mean, float* running_var, int64_t* num_batches_tracked, float momentum, float eps,

@@ -277,14 +277,17 @@ def _dgrad(d, dy, wd, dx, addend_ptr, src, dtype):
     _lib.call('fva_conv_dgrad', C.byref(d), _p(dy), _p(wd), _p(dx), C.c_void_p(addend_ptr or 0), _stream())
 
 
-def _wgrad_dgrad(d, x_ptr, dy, wd, wshape, hold, weight, need_dx, addend_ptr=None, src=None):
+def _wgrad_dgrad(d, x_ptr, dy, wd, wshape, hold, weight, need_dx, addend_ptr=None, src=None, need_dw=True):
     """The tail of a convolution block's backward pass, given dy (halo NHWC): dW by fva_conv_wgrad on wgrad_stream(), then, if asked for,
     dx by _dgrad (``addend_ptr`` / ``src``: its fusion arguments; the VGG blocks have none).  ``hold``: what the side stream must keep
-    alive besides dy and the workspace (the saved input).  Returns (dx_buf or None, dw)."""
-    dw = torch.empty(wshape, dtype=torch.float32, device=dy.device)
-    ws_bytes = _lib.load().fva_conv_wgrad_workspace(C.byref(d))
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dy.device)
-    _lib.call('fva_conv_wgrad', C.byref(d), C.c_void_p(x_ptr), _p(dy), _p(dw), 0, _p(ws), ws_bytes, wgrad_stream(hold + (dy, ws), weight))     # NOT dw: a second reference makes AccumulateGrad clone it (on the main stream)
+    alive besides dy and the workspace (the saved input).  Returns (dx_buf or None, dw); ``need_dw=False`` (a frozen-statistics block
+    whose weight asks for no gradient) launches no weight gradient and returns None for it."""
+    dw = None
+    if need_dw:
+        dw = torch.empty(wshape, dtype=torch.float32, device=dy.device)
+        ws_bytes = _lib.load().fva_conv_wgrad_workspace(C.byref(d))
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dy.device)
+        _lib.call('fva_conv_wgrad', C.byref(d), C.c_void_p(x_ptr), _p(dy), _p(dw), 0, _p(ws), ws_bytes, wgrad_stream(hold + (dy, ws), weight))     # NOT dw: a second reference makes AccumulateGrad clone it (on the main stream)
     dx = None
     if need_dx:
         dx = torch.empty((d.B, d.H, d.W, d.Cin), dtype=dy.dtype, device=dy.device)
@@ -541,6 +544,7 @@ def conv_block_fwd(x, x_ptr, x_pad, weight, gamma, beta, bn, training, stride, d
         s.gamma, s.dtype, s.OH, s.OW, s.M, s.wshape = gamma, dtype, OH, OW, M, tuple(weight.shape)
         s.weight = weight
         s.training = training
+        s.bn = None if training else bn                 # frozen statistics: the backward pass reads the running mean / variance
         s.x_src, s.consumers, s.fused = x_src, 0, None
         s.acc = fin.state if fin is not None else None
         if training:
@@ -760,10 +764,41 @@ def wgrad_stream(buffers, weight=None):
     return side
 
 
-def conv_block_bwd(s, dz_ptr, need_dx, addend_ptr=None):
-    """Backward of conv_block_fwd given dz (dense NHWC, dtype).  Returns (dx_buf or None, dw, dgamma, dbeta)."""
+def frozen_bn_bwd(act, code, dz_ptr, y, scale, shift, bn, bias, dy, dy_pad, B, H, W, Cout, need_gamma, need_beta, need_bias=False):
+    """BatchNorm backward with frozen statistics (the module in eval mode): ONE pass writes dy = scale * dU (halo form dy_pad = 1, dense
+    form dy_pad = 0) and, when gamma, beta or the convolution bias ``bias`` in front of the BatchNorm asks for a gradient, the partial
+    sums that fva_bn_frozen_bwd_finalize folds.  ``act``: 'silu' or 'relu'.  Returns (dgamma, dbeta, dbias), None where not asked for."""
+    name = f'fva_bn_{act}_frozen_bwd'
+    if not (need_gamma or need_beta or need_bias):
+        _lib.call(name, code, C.c_void_p(dz_ptr), _p(y), _p(scale), _p(shift), None, None, None, _p(dy), dy_pad, B, H, W, Cout, _stream())
+        return None, None, None
+    lib, dev = _lib.load(), y.device
+    m = torch.empty(Cout, dtype=torch.float32, device=dev)
+    r = torch.empty_like(m)
+    _lib.call('fva_bn_frozen_stats', Cout, _p(bn.rm), _p(bn.rv), _p(bias), bn.eps, _p(m), _p(r), _stream())
+    nb = lib.fva_bn_frozen_bwd_blocks(code, B, H, W, Cout, dy_pad)
+    part = torch.empty((lib.fva_bn_partial_rows(nb), 2, Cout), dtype=torch.float32, device=dev)
+    _lib.call(name, code, C.c_void_p(dz_ptr), _p(y), _p(scale), _p(shift), _p(m), _p(r), _p(part), _p(dy), dy_pad, B, H, W, Cout, _stream())
+    dgamma = torch.empty(Cout, dtype=torch.float32, device=dev) if need_gamma else None
+    dbeta = torch.empty(Cout, dtype=torch.float32, device=dev) if need_beta else None
+    dbias = torch.empty(Cout, dtype=torch.float32, device=dev) if need_bias else None
+    _lib.call('fva_bn_frozen_bwd_finalize', _p(part), nb, part.shape[0], Cout, _p(scale), _p(dgamma), _p(dbeta), _p(dbias), _stream())
+    return dgamma, dbeta, dbias
+
+
+def conv_block_bwd(s, dz_ptr, need_dx, addend_ptr=None, needs=(True, True, True)):
+    """Backward of conv_block_fwd given dz (dense NHWC, dtype).  Returns (dx_buf or None, dw, dgamma, dbeta).  ``needs``: whether the weight,
+    gamma and beta ask for a gradient -- read by the frozen-statistics branch alone, which computes only what is asked for."""
     if not s.training:
-        raise RuntimeError('fastvision_amd: backward through an eval-mode BatchNorm block is not supported')
+        d = s.d
+        dy = torch.empty((d.B, s.OH + 2, s.OW + 2, d.Cout), dtype=s.dtype, device=s.y.device)
+        dgamma, dbeta, _ = frozen_bn_bwd('silu', _code(s.dtype), dz_ptr, s.y, s.scale, s.shift, s.bn, None, dy, 1, d.B, s.OH, s.OW, d.Cout,
+                                         needs[1], needs[2])
+        dx, dw = _wgrad_dgrad(d, s.x_ptr, dy, s.wd, s.wshape, (s.x, getattr(s, 'keep', None)), s.weight, need_dx, addend_ptr, s.x_src,
+                              need_dw=needs[0])
+        s.__dict__.clear()
+        s.training, s.consumers, s.fused = False, 0, None
+        return dx, dw, dgamma, dbeta
     lib = _lib.load()
     d, dtype, dev = s.d, s.dtype, s.y.device
     Cout, code = d.Cout, _code(s.dtype)
@@ -831,9 +866,29 @@ class ConvBNSiLUFn(torch.autograd.Function):
         if s is None:
             raise _released('ConvBlock')
         keep, dz_ptr = to_dense(dz, s.dtype)
-        dx, dw, dg, db = conv_block_bwd(s, dz_ptr, ctx.needs_input_grad[0])
+        dx, dw, dg, db = conv_block_bwd(s, dz_ptr, ctx.needs_input_grad[0], needs=ctx.needs_input_grad[1:4])
         x_like, ctx.s, ctx.x_like = ctx.x_like, None, None       # like torch's saved tensors: released by the backward pass that used them
         return (_grad_like(dx, x_like) if dx is not None else None), dw, dg, db, None, None, None, None
+
+
+def _stem_wgrad_mfma(img4, dy, B, Cin, H, W, Cout):
+    """conv0's weight gradient from the halo dY and the packed NHWC4 image: 3 vertical taps over 4-pixel windows on MFMA."""
+    lib, dev = _lib.load(), dy.device
+    raw = torch.empty((Cout, 4, 4, 3), dtype=torch.float32, device=dev)        # [co][kw][ci][kh]
+    wsb = lib.fva_stem_wgrad_mfma_workspace()
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    _lib.call('fva_stem_wgrad_mfma', _p(img4), _p(dy), _p(raw), _p(ws), wsb, B, H, W, _stream())
+    return raw[:, :3, :Cin, :].permute(0, 2, 3, 1).contiguous()
+
+
+def _stem_wgrad_direct(code, img, dy, wshape, B, Cin, H, W, Cout):
+    """conv0's weight gradient from the dense dY and the fp32 images."""
+    lib, dev = _lib.load(), dy.device
+    dw = torch.empty(wshape, dtype=torch.float32, device=dev)
+    wsb = lib.fva_stem_wgrad_workspace(B, Cin, H, W, Cout)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    _lib.call('fva_stem_wgrad', code, _p(img), _p(dy), _p(dw), 0, _p(ws), wsb, B, Cin, H, W, Cout, _stream())
+    return dw
 
 
 class StemFn(torch.autograd.Function):
@@ -856,7 +911,10 @@ class StemFn(torch.autograd.Function):
         mean = rstd = None
         wsb = lib.fva_stem_fwd_workspace(code, B, H, W)           # bf16 NHWC4 copy of the images for the MFMA kernel
         ws = torch.empty(wsb, dtype=torch.uint8, device=dev) if wsb else None
-        if ws is not None and os.environ.get('FVA_STEM_FUSED', '1') != '0':
+        # frozen statistics under training: the one-pass backward reads y, so the forward takes the path that stores it
+        frozen = not training and _GRAD_ON[0] and any(ctx.needs_input_grad)
+        ctx.bn = bn if frozen else None
+        if ws is not None and os.environ.get('FVA_STEM_FUSED', '1') != '0' and not frozen:
             # bf16: conv0's pre-BN output is never stored; the statistics pass and the apply pass each recompute it on MFMA
             # from the packed image (839 MB of HBM traffic saved per pass at B = 32, 640 px)
             _lib.call('fva_stem_pack', _p(img), _p(ws), wsb, B, Cin, H, W, _stream())
@@ -898,9 +956,8 @@ class StemFn(torch.autograd.Function):
             raise _released('stem')
         img, y, scale, shift, mean, rstd, gamma, dtype, training, wshape = ctx.saved
         img4, w_saved = ctx.img4, getattr(ctx, 'weight', None)
+        bn, ctx.bn = getattr(ctx, 'bn', None), None
         ctx.saved = ctx.img4 = ctx.weight = None                  # released by the backward pass that uses them
-        if not training:
-            raise RuntimeError('fastvision_amd: backward through an eval-mode BatchNorm block is not supported')
         if ctx.needs_input_grad[0]:
             raise RuntimeError('fastvision_amd: the stem does not produce a gradient for the input images')
         lib = _lib.load()
@@ -908,6 +965,8 @@ class StemFn(torch.autograd.Function):
         Cout, code, dev = wshape[0], _code(dtype), img.device
         M = B * H * W
         keep, dz_ptr = to_dense(dz, dtype)
+        if y is None and not training:
+            raise RuntimeError('fastvision_amd: the stem ran its fused inference path (gradients were off in forward): nothing was saved for backward')
         if y is None:
             # fused bf16 path: both BatchNorm-backward passes recompute conv0 from the packed image, dY lands in a halo buffer
             w = w_saved
@@ -922,11 +981,18 @@ class StemFn(torch.autograd.Function):
             dy = torch.empty((B, H + 2, W + 2, Cout), dtype=dtype, device=dev)
             _lib.call('fva_stem_fused', 3, _p(img4), _p(w), C.c_void_p(dz_ptr), _p(scale), _p(shift), _p(mean), _p(rstd), _p(coef),
                       _p(dy), None, B, Cin, H, W, _stream())
-            raw = torch.empty((Cout, 4, 4, 3), dtype=torch.float32, device=dev)        # [co][kw][ci][kh]
-            wsb = lib.fva_stem_wgrad_mfma_workspace()
-            ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-            _lib.call('fva_stem_wgrad_mfma', _p(img4), _p(dy), _p(raw), _p(ws), wsb, B, H, W, _stream())
-            return None, raw[:, :3, :Cin, :].permute(0, 2, 3, 1).contiguous(), dgamma, dbeta, None, None, None
+            return None, _stem_wgrad_mfma(img4, dy, B, Cin, H, W, Cout), dgamma, dbeta, None, None, None
+        # MFMA path: dY as a halo buffer, conv0 seen as 3 vertical taps over 4-pixel windows of the NHWC4 image; else dense dY, direct kernel
+        mfma = img4 is not None and os.environ.get('FVA_STEM_WGRAD_MFMA', '1') != '0'
+        if not training:
+            # frozen statistics: one pass forms dY (and the sums of dgamma / dbeta when asked for); only what autograd asks for is computed
+            need_w, need_g, need_b = ctx.needs_input_grad[1:4]
+            dy = torch.empty((B, H + 2, W + 2, Cout) if mfma else (M, Cout), dtype=dtype, device=dev)
+            dgamma, dbeta, _ = frozen_bn_bwd('silu', code, dz_ptr, y, scale, shift, bn, None, dy, 1 if mfma else 0, B, H, W, Cout, need_g, need_b)
+            dw = None
+            if need_w:
+                dw = _stem_wgrad_mfma(img4, dy, B, Cin, H, W, Cout) if mfma else _stem_wgrad_direct(code, img, dy, wshape, B, Cin, H, W, Cout)
+            return None, dw, dgamma, dbeta, None, None, None
         nb = lib.fva_bn_bwd_blocks(code, M, Cout)
         part = torch.empty((lib.fva_bn_partial_rows(nb), 2, Cout), dtype=torch.float32, device=dev)
         _lib.call('fva_bn_silu_bwd_reduce', code, C.c_void_p(dz_ptr), _p(y), _p(scale), _p(shift), _p(mean), _p(rstd), _p(part),
@@ -935,25 +1001,15 @@ class StemFn(torch.autograd.Function):
         dbeta = torch.empty_like(dgamma)
         coef = torch.empty((3, Cout), dtype=torch.float32, device=dev)
         _lib.call('fva_bn_bwd_finalize', _p(part), nb, part.shape[0], M, Cout, _p(gamma), _p(rstd), _p(dgamma), _p(dbeta), 0, _p(coef), _stream())
-        if img4 is not None and os.environ.get('FVA_STEM_WGRAD_MFMA', '1') != '0':
-            # MFMA path: dY as a halo buffer, conv0 seen as 3 vertical taps over 4-pixel windows of the NHWC4 image
+        if mfma:
             dy = torch.empty((B, H + 2, W + 2, Cout), dtype=dtype, device=dev)
             _lib.call('fva_bn_silu_bwd_apply', code, C.c_void_p(dz_ptr), _p(y), _p(scale), _p(shift), _p(mean), _p(rstd), _p(coef),
                       _p(dy), 1, B, H, W, Cout, _stream())
-            raw = torch.empty((Cout, 4, 4, 3), dtype=torch.float32, device=dev)        # [co][kw][ci][kh]
-            wsb = lib.fva_stem_wgrad_mfma_workspace()
-            ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-            _lib.call('fva_stem_wgrad_mfma', _p(img4), _p(dy), _p(raw), _p(ws), wsb, B, H, W, _stream())
-            dw = raw[:, :3, :Cin, :].permute(0, 2, 3, 1).contiguous()
-            return None, dw, dgamma, dbeta, None, None, None
+            return None, _stem_wgrad_mfma(img4, dy, B, Cin, H, W, Cout), dgamma, dbeta, None, None, None
         dy = torch.empty((M, Cout), dtype=dtype, device=dev)
         _lib.call('fva_bn_silu_bwd_apply', code, C.c_void_p(dz_ptr), _p(y), _p(scale), _p(shift), _p(mean), _p(rstd), _p(coef),
                   _p(dy), 0, B, H, W, Cout, _stream())
-        dw = torch.empty(wshape, dtype=torch.float32, device=dev)
-        wsb = lib.fva_stem_wgrad_workspace(B, Cin, H, W, Cout)
-        ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-        _lib.call('fva_stem_wgrad', code, _p(img), _p(dy), _p(dw), 0, _p(ws), wsb, B, Cin, H, W, Cout, _stream())
-        return None, dw, dgamma, dbeta, None, None, None
+        return None, _stem_wgrad_direct(code, img, dy, wshape, B, Cin, H, W, Cout), dgamma, dbeta, None, None, None
 
 
 class ResidualFn(torch.autograd.Function):
@@ -979,8 +1035,8 @@ class ResidualFn(torch.autograd.Function):
         if s1 is None:
             raise _released('ResidualBlock')
         keep, dout_ptr = to_dense(dout, s1.dtype)
-        dz1, dw2, dg2, db2 = conv_block_bwd(s2, dout_ptr, True)
-        dx, dw1, dg1, db1 = conv_block_bwd(s1, dz1.data_ptr(), ctx.needs_input_grad[0], addend_ptr=dout_ptr)
+        dz1, dw2, dg2, db2 = conv_block_bwd(s2, dout_ptr, True, needs=ctx.needs_input_grad[5:8])
+        dx, dw1, dg1, db1 = conv_block_bwd(s1, dz1.data_ptr(), ctx.needs_input_grad[0], addend_ptr=dout_ptr, needs=ctx.needs_input_grad[1:4])
         gx = _grad_like(dx, ctx.x_like) if dx is not None else None
         ctx.s1 = ctx.s2 = ctx.x_like = None                       # released by the backward pass that used them
         return gx, dw1, dg1, db1, None, dw2, dg2, db2, None, None, None
@@ -1118,6 +1174,7 @@ def conv_bn_silu(x, conv, bn, stride=None, dtype=None):
 
 def stem(images, conv, bn, dtype=None):
     dtype = dtype or get_compute_dtype()
+    _GRAD_ON[0] = torch.is_grad_enabled()
     return StemFn.apply(images, conv.weight, bn.weight, bn.bias, _BNState(bn), bn.training, dtype)
 
 

@@ -19,8 +19,8 @@ import torch.nn.functional as F
 
 from . import _lib
 from .fc_ops import rows_as
-from .ops import (_BNState, _code, _grad_like, _p, _stream, _wgrad_dgrad, dense_view, flush_pending_apply, get_compute_dtype, halo_alloc, halo_info,
-                  packed_weights, require_gpu, to_dense, to_halo)
+from .ops import (_BNState, _code, _grad_like, _p, _released, _stream, _wgrad_dgrad, dense_view, flush_pending_apply, frozen_bn_bwd, get_compute_dtype,
+                  halo_alloc, halo_info, packed_weights, require_gpu, to_dense, to_halo)
 
 __all__ = ['conv_bias_relu', 'max_pool2', 'conv_bn_relu', 'adaptive_avg_pool7_flatten']
 
@@ -118,7 +118,9 @@ class ConvBNReLUFn(torch.autograd.Function):
     """``relu(bn(conv(x) + b))``.  The bias cancels in the training-mode output (the batch mean takes it away again), so the convolution
     runs without it and the bias is accounted for where it stays visible: running_mean tracks mean(y) + b (fva_bn_bias_running_mean) and
     the eval-mode shift is beta + (b - running_mean) * scale (fva_bn_eval_coeffs_bias).  Its gradient is the channel sum of dy, which the
-    BatchNorm backward makes zero up to rounding: returned as exact zeros (a real fp32 tensor, for optimizers with weight decay)."""
+    BatchNorm backward makes zero up to rounding: returned as exact zeros (a real fp32 tensor, for optimizers with weight decay).
+    With frozen statistics (the BatchNorm in eval mode, gradients on) nothing cancels: u = (y + b - running_mean) * scale_bn + beta, the
+    one-pass backward (ops.frozen_bn_bwd, ReLU form) takes m = running_mean - b, and dbias = scale * sum dU is a real gradient."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, gamma, beta, bn, training, dtype):
@@ -152,20 +154,30 @@ class ConvBNReLUFn(torch.autograd.Function):
             _lib.call('fva_bn_eval_coeffs_bias', Cout, _p(gamma), _p(beta), _p(bn.rm), _p(bn.rv), _p(b32), bn.eps, _p(scale), _p(shift), _stream())
         zbuf, z = halo_alloc(B, Cout, H, W, dtype, dev, 1)
         _lib.call('fva_bn_relu_apply', code, _p(y), _p(scale), _p(shift), _p(zbuf), 1, B, H, W, Cout, _stream())
-        ctx.saved = (keep, x_ptr, y, scale, shift, mean, rstd, d, wd, dtype, tuple(weight.shape), gamma) if training else None
-        ctx.training = training
+        need = training or any(ctx.needs_input_grad)
+        ctx.saved = (keep, x_ptr, y, scale, shift, mean, rstd, d, wd, dtype, tuple(weight.shape), gamma) if need else None
+        ctx.training, ctx.bn, ctx.b32 = training, (None if training else bn), (None if training else b32)
         ctx.x_like, ctx.weight = x, weight
         return z
 
     @staticmethod
     def backward(ctx, dz):
-        if not ctx.training:
-            raise RuntimeError('fastvision_amd: backward through an eval-mode BatchNorm block is not supported')
+        if ctx.saved is None:
+            raise _released('conv_bn_relu')
         keep, x_ptr, y, scale, shift, mean, rstd, d, wd, dtype, wshape, gamma = ctx.saved
         lib = _lib.load()
         B, H, W, Cout, dev, code = d.B, d.H, d.W, d.Cout, y.device, _code(dtype)
         M = B * H * W
         keep_dz, dz_ptr = to_dense(dz, dtype)
+        if not ctx.training:
+            # frozen statistics: one pass, and only what autograd asks for
+            need_x, need_w, need_bias, need_g, need_b = ctx.needs_input_grad[:5]
+            dy = torch.empty((B, H + 2, W + 2, Cout), dtype=dtype, device=dev)
+            dgamma, dbeta, dbias = frozen_bn_bwd('relu', code, dz_ptr, y, scale, shift, ctx.bn, ctx.b32, dy, 1, B, H, W, Cout, need_g, need_b, need_bias)
+            dxb, dw = _wgrad_dgrad(d, x_ptr, dy, wd, wshape, (keep,), ctx.weight, need_x, need_dw=need_w)
+            dx = _grad_like(dxb, ctx.x_like) if dxb is not None else None
+            ctx.saved = ctx.x_like = ctx.weight = ctx.bn = ctx.b32 = None
+            return dx, dw, dbias, dgamma, dbeta, None, None, None
         nb = lib.fva_bn_bwd_blocks(code, M, Cout)
         part = torch.empty((lib.fva_bn_partial_rows(nb), 2, Cout), dtype=torch.float32, device=dev)
         _lib.call('fva_bn_relu_bwd_reduce', code, C.c_void_p(dz_ptr), _p(y), _p(scale), _p(shift), _p(mean), _p(rstd), _p(part), nb, M, Cout, _stream())

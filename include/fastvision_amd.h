@@ -686,6 +686,25 @@ int fva_bn_relu_bwd_apply(int dtype, const void* dz, const void* y, const float*
 int fva_bn_bias_running_mean(int32_t C, float* running_mean, const float* bias, float momentum, void* stream);
 int fva_bn_eval_coeffs_bias(int32_t C, const float* gamma, const float* beta, const float* rm, const float* rv, const float* bias, float eps,
                             float* scale, float* shift, void* stream);
+
+/* ---- BatchNorm backward with FROZEN statistics (the module in eval mode, its convolution and affine parameters training; version 7) ----
+ * scale / shift (fva_bn_eval_coeffs[_bias]) do not depend on the batch, so the two passes above collapse into one over dz and y (dense
+ * NHWC [B*H*W][C]):
+ *   dy = scale * dU,  dU = dz * act'(y * scale + shift)     halo buffer [B][H+2p][W+2p][C] with its zero border, p = dy_pad (0 or 1)
+ *   partial != NULL: one row [2][C] per block of the launch (fva_bn_frozen_bwd_blocks() rows; fixed order, no atomics) holding
+ *   s1 = sum dU and s2 = sum dU * (y - m) * r, with m, r from fva_bn_frozen_stats: m = running_mean (- bias), r = 1 / sqrt(running_var + eps).
+ *   partial == NULL (neither gamma nor beta asks for a gradient): only dy is written; m and r are not read.
+ * C / (16-byte chunk) a power of two <= 256.  fva_bn_frozen_bwd_finalize folds the table (allocated with
+ * fva_bn_partial_rows(nblocks) rows) into dbeta = s1, dgamma = s2 and dbias = scale * s1 (the gradient of a convolution bias in front
+ * of the BatchNorm); each of the three may be NULL. */
+int32_t fva_bn_frozen_bwd_blocks(int dtype, int B, int H, int W, int C, int dy_pad);
+int fva_bn_silu_frozen_bwd(int dtype, const void* dz, const void* y, const float* scale, const float* shift, const float* m, const float* r,
+                           float* partial, void* dy, int dy_pad, int B, int H, int W, int C, void* stream);
+int fva_bn_relu_frozen_bwd(int dtype, const void* dz, const void* y, const float* scale, const float* shift, const float* m, const float* r,
+                           float* partial, void* dy, int dy_pad, int B, int H, int W, int C, void* stream);
+int fva_bn_frozen_bwd_finalize(float* partial, int32_t nblocks, int32_t partial_rows, int C, const float* scale, float* dgamma, float* dbeta,
+                               float* dbias, void* stream);
+int fva_bn_frozen_stats(int32_t C, const float* rm, const float* rv, const float* bias, float eps, float* m, float* r, void* stream);
 /* nn.AdaptiveAvgPool2d((7, 7)) + torch.flatten(x, 1).  x: NHWC [B][H+2*x_pad][W+2*x_pad][C] of dtype; out [B][C*49] of dtype in the
  * order c * 49 + i * 7 + j; windows floor(i*H/7) .. ceil((i+1)*H/7) as torch defines them, any H, W >= 1; C a multiple of the 16-byte
  * chunk.  Backward (gather form, no atomics): g [B][C*49] of dtype -> dx dense NHWC [B][H][W][C] of dtype.  One launch each;
