@@ -904,10 +904,6 @@ __global__ __launch_bounds__((BM / 64) * (BN / 64) * 64) void igemm_kernel(const
         store_tile_bf16<EPI, BM, BN, NT, PITCH>(p, smem, tid, n0, mblk, [&](int row) { const int m = m0 + row; return m < p.M ? out_pixel(m) : (int64_t)-1; },
                                                 EPI == EPI_BNB ? y_pre : nullptr, PREFETCH ? a_pre : nullptr, coef_tab);
     }
-    if constexpr (AX) {
-        // the blocks of this launch were the consumers of the previous block's accumulator: the last one to get here zeroes it
-
-    }
     stamp(5);
 }
 
@@ -1656,19 +1652,25 @@ int launch_igemm8(const IgemmParams& p, hipStream_t s) {
 
 inline bool wide_tile(int N) { return N >= 128; }
 
-// 128x128 tiles for N >= 128, 256x64 for thinner outputs (the rows of BatchNorm partial statistics follow the tile)
-inline int tile_bm(int /*dtype*/, int /*M*/, int N) { return wide_tile(N) ? 128 : 256; }
+// THE choice of the implicit-GEMM kernel and of its tile rows BM (the rows of BatchNorm partial statistics follow the tile): the
+// 8-phase 256x256 kernel where use_igemm8 takes the layer (never the head's epilogue, never half-row k-tiles), else 128x128 tiles
+// for N >= 128 and 256x64 for thinner outputs.  ntaps: real taps of the launch; in_pixels: see use_igemm8.
+enum { IGEMM_128, IGEMM_256x64, IGEMM_8PHASE };
+struct IgemmChoice {
+    int kernel, bm;
+};
+inline IgemmChoice choose_igemm(int dtype, int64_t M, int N, int C, int ntaps, int64_t in_pixels, bool halfrow, bool head) {
+    if (!head && !halfrow && use_igemm8(dtype, M, N, C, ntaps, in_pixels)) return {IGEMM_8PHASE, 256};
+    return wide_tile(N) ? IgemmChoice{IGEMM_128, 128} : IgemmChoice{IGEMM_256x64, 256};
+}
 
 template <int EPI>
-int launch_igemm(int dtype, const IgemmParams& p, hipStream_t s) {
-    if (dtype == FVA_BF16) {
-        if constexpr (EPI != EPI_HEAD) {
-            if (!p.halfrow && use_igemm8(dtype, p.M, p.N, p.C, p.ktiles / p.kt_per_tap, (int64_t)(p.M / p.OHW + 1) * p.in_img))
-                return launch_igemm8<EPI>(p, s);
-        }
-        return wide_tile(p.N) ? launch_one<bf16_t, 128, 128, EPI, 2>(p, s) : launch_one<bf16_t, 256, 64, EPI, 2>(p, s);
+int launch_igemm(IgemmChoice c, int dtype, const IgemmParams& p, hipStream_t s) {
+    if constexpr (EPI != EPI_HEAD) {
+        if (c.kernel == IGEMM_8PHASE) return launch_igemm8<EPI>(p, s);
     }
-    return wide_tile(p.N) ? launch_one<float, 128, 128, EPI, 2>(p, s) : launch_one<float, 256, 64, EPI, 2>(p, s);
+    if (dtype == FVA_BF16) return c.kernel == IGEMM_128 ? launch_one<bf16_t, 128, 128, EPI, 2>(p, s) : launch_one<bf16_t, 256, 64, EPI, 2>(p, s);
+    return c.kernel == IGEMM_128 ? launch_one<float, 128, 128, EPI, 2>(p, s) : launch_one<float, 256, 64, EPI, 2>(p, s);
 }
 
 int check_desc(const fva_conv_desc* d, const char* who) {
@@ -1752,59 +1754,73 @@ __global__ void pack_weights_kernel(const float* __restrict__ w, void* fwd, void
     }
 }
 
-// All conv layers of a model in ONE launch: blockIdx.y selects the table entry (one per layer); each block walks
-// 32 (Cout) x 32 (Cin) tiles of that layer.  A tile's k*k taps are read as contiguous runs of the OIHW source,
-// staged in LDS and written out as 64-byte (bf16) rows of both operand layouts.
-__global__ __launch_bounds__(256) void pack_weights_multi_kernel(const fva_pack_entry* __restrict__ table) {
-    __shared__ float tile[32][32 * 9 + 1];
-    const fva_pack_entry e = table[blockIdx.y];
+typedef float PackTile[32][32 * 9 + 1];
+
+__device__ __forceinline__ void store_packed(void* p, int64_t o, float v, bool bf) {
+    if (bf) ((bf16_t*)p)[o] = (bf16_t)v; else ((float*)p)[o] = v;
+}
+
+// One 32 (Cout) x 32 (Cin) tile of layer e at (co0, ci0), element by element (256 threads): its k*k taps are read as contiguous runs of
+// the OIHW source, staged in LDS and written out as rows of both operand layouts; ragged tiles are masked.
+__device__ void pack_tile_elementwise(const fva_pack_entry& e, PackTile& tile, int co0, int ci0, int tid) {
     const int kk = e.ksize * e.ksize;
-    const int tco = (e.Cout + 31) / 32, tci = (e.Cin + 31) / 32;
     const bool bf = e.dtype == FVA_BF16;
-    for (int tl = blockIdx.x; tl < tco * tci; tl += gridDim.x) {
-        const int co0 = (tl / tci) * 32, ci0 = (tl % tci) * 32;
-        const int ncol = (e.Cin - ci0 < 32 ? e.Cin - ci0 : 32) * kk;   // contiguous floats per co row
-        for (int i = threadIdx.x; i < 32 * 32 * kk; i += 256) {
-            const int r = i / (32 * kk), c = i - r * (32 * kk);
-            tile[r][c] = (co0 + r < e.Cout && c < ncol) ? e.w[((int64_t)(co0 + r) * e.Cin + ci0) * kk + c] : 0.f;
-        }
-        __syncthreads();
-        const int a = threadIdx.x >> 5, l = threadIdx.x & 31;        // 8 rows at a time, 32 lanes along the row
-        for (int t = 0; t < kk; ++t) {
+    const int ncol = (e.Cin - ci0 < 32 ? e.Cin - ci0 : 32) * kk;   // contiguous floats per co row
+    for (int i = tid; i < 32 * 32 * kk; i += 256) {
+        const int r = i / (32 * kk), c = i - r * (32 * kk);
+        tile[r][c] = (co0 + r < e.Cout && c < ncol) ? e.w[((int64_t)(co0 + r) * e.Cin + ci0) * kk + c] : 0.f;
+    }
+    __syncthreads();
+    const int a = tid >> 5, l = tid & 31;        // 8 rows at a time, 32 lanes along the row
+    for (int t = 0; t < kk; ++t) {
 #pragma unroll
-            for (int rr = 0; rr < 32; rr += 8) {
-                const int r = rr + a;
-                // forward layout [t][co][ci]: row = co, lanes along ci
-                if (e.w_fwd && co0 + r < e.Cout && ci0 + l < e.Cin) {
-                    const int64_t o = ((int64_t)t * e.Cout + co0 + r) * e.Cin + ci0 + l;
-                    const float v = tile[r][l * kk + t];
-                    if (bf) ((bf16_t*)e.w_fwd)[o] = (bf16_t)v; else ((float*)e.w_fwd)[o] = v;
-                }
-                // dgrad layout [t][ci][co]: row = ci, lanes along co
-                if (e.w_dgrad && ci0 + r < e.Cin && co0 + l < e.Cout) {
-                    const float v = tile[l][r * kk + t];
-                    if (e.dgrad_paired) {
-                        const int64_t row = paired_row(t, ci0 + r, e.Cin);
-                        const int64_t o = row * e.Cout + co0 + l;
-                        if (bf) ((bf16_t*)e.w_dgrad)[o] = (bf16_t)v; else ((float*)e.w_dgrad)[o] = v;
-                        if (t % 3 == 0) {
-                            const int64_t z = (row - e.Cin) * e.Cout + co0 + l;
-                            if (bf) ((bf16_t*)e.w_dgrad)[z] = (bf16_t)0.f; else ((float*)e.w_dgrad)[z] = 0.f;
-                        }
-                    } else {
-                        const int64_t o = ((int64_t)t * e.Cin + ci0 + r) * e.Cout + co0 + l;
-                        if (bf) ((bf16_t*)e.w_dgrad)[o] = (bf16_t)v; else ((float*)e.w_dgrad)[o] = v;
-                    }
+        for (int rr = 0; rr < 32; rr += 8) {
+            const int r = rr + a;
+            // forward layout [t][co][ci]: row = co, lanes along ci
+            if (e.w_fwd && co0 + r < e.Cout && ci0 + l < e.Cin)
+                store_packed(e.w_fwd, ((int64_t)t * e.Cout + co0 + r) * e.Cin + ci0 + l, tile[r][l * kk + t], bf);
+            // dgrad layout [t][ci][co]: row = ci, lanes along co
+            if (e.w_dgrad && ci0 + r < e.Cin && co0 + l < e.Cout) {
+                const float v = tile[l][r * kk + t];
+                if (e.dgrad_paired) {
+                    const int64_t row = paired_row(t, ci0 + r, e.Cin);
+                    store_packed(e.w_dgrad, row * e.Cout + co0 + l, v, bf);
+                    if (t % 3 == 0) store_packed(e.w_dgrad, (row - e.Cin) * e.Cout + co0 + l, 0.f, bf);   // the x-even half of a dxo=1 tap is zero
+                } else {
+                    store_packed(e.w_dgrad, ((int64_t)t * e.Cin + ci0 + r) * e.Cout + co0 + l, v, bf);
                 }
             }
         }
-        __syncthreads();
     }
-    // zero pad tap (bf16 half-row k-tiles): taps_* may exceed k*k by one
+}
+
+// the tile's share of the zero pad tap (bf16 half-row k-tiles): taps_* may exceed k*k by one
+__device__ void pack_tile_pad_tap(const fva_pack_entry& e, int co0, int ci0, int tid) {
+    const int kk = e.ksize * e.ksize;
+    const bool pad_f = e.w_fwd && e.taps_fwd > kk, pad_d = e.w_dgrad && !e.dgrad_paired && e.taps_dgrad > kk;
+    if (!pad_f && !pad_d) return;
+    const bool bf = e.dtype == FVA_BF16;
     const int64_t cc = (int64_t)e.Cout * e.Cin;
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < cc; i += (int64_t)gridDim.x * blockDim.x) {
-        if (e.w_fwd && e.taps_fwd > kk) { if (bf) ((bf16_t*)e.w_fwd)[kk * cc + i] = (bf16_t)0.f; else ((float*)e.w_fwd)[kk * cc + i] = 0.f; }
-        if (e.w_dgrad && !e.dgrad_paired && e.taps_dgrad > kk) { if (bf) ((bf16_t*)e.w_dgrad)[kk * cc + i] = (bf16_t)0.f; else ((float*)e.w_dgrad)[kk * cc + i] = 0.f; }
+    for (int i = tid; i < 32 * 32; i += 256) {
+        const int r = i >> 5, c = i & 31;
+        if (co0 + r < e.Cout && ci0 + c < e.Cin) {
+            if (pad_f) store_packed(e.w_fwd, kk * cc + (int64_t)(co0 + r) * e.Cin + ci0 + c, 0.f, bf);
+            if (pad_d) store_packed(e.w_dgrad, kk * cc + (int64_t)(ci0 + c) * e.Cout + co0 + r, 0.f, bf);
+        }
+    }
+}
+
+// All conv layers of a model in ONE launch: blockIdx.y selects the table entry (one per layer); each block walks
+// 32 (Cout) x 32 (Cin) tiles of that layer.
+__global__ __launch_bounds__(256) void pack_weights_multi_kernel(const fva_pack_entry* __restrict__ table) {
+    __shared__ PackTile tile;
+    const fva_pack_entry e = table[blockIdx.y];
+    const int tco = (e.Cout + 31) / 32, tci = (e.Cin + 31) / 32;
+    for (int tl = blockIdx.x; tl < tco * tci; tl += gridDim.x) {
+        const int co0 = (tl / tci) * 32, ci0 = (tl % tci) * 32;
+        pack_tile_elementwise(e, tile, co0, ci0, threadIdx.x);
+        pack_tile_pad_tap(e, co0, ci0, threadIdx.x);
+        __syncthreads();
     }
 }
 
@@ -1813,9 +1829,9 @@ __global__ __launch_bounds__(256) void pack_weights_multi_kernel(const fva_pack_
 // index by 32 k^2 and its stores are 2 bytes per lane -- 287 us per step for 0.5 GB (1.7 TB/s).  Here the caller numbers the tiles
 // of all layers consecutively (entry.tile_start = tiles of the entries before it), a block finds its layer by bisection, aligned
 // tiles (k = 3 or 1, whole 32 x 32) load 16 bytes per lane and store four bf16 per lane (whole 64-byte rows); ragged or fp32
-// tiles and the paired layout take the element-wise path of the kernel above.
+// tiles and the paired layout take the element-wise path (pack_tile_elementwise).
 __global__ __launch_bounds__(256) void pack_weights_tiled_kernel(const fva_pack_entry* __restrict__ table, int n) {
-    __shared__ float tile[32][32 * 9 + 1];
+    __shared__ PackTile tile;
     int lo = 0, hi = n - 1;                       // last entry whose tile_start <= blockIdx.x
     while (lo < hi) {
         const int mid = (lo + hi + 1) >> 1;
@@ -1853,57 +1869,9 @@ __global__ __launch_bounds__(256) void pack_weights_tiled_kernel(const fva_pack_
             }
         }
     } else {
-        const int ncol = (e.Cin - ci0 < 32 ? e.Cin - ci0 : 32) * kk;
-        for (int i = tid; i < 32 * 32 * kk; i += 256) {
-            const int r = i / (32 * kk), c = i - r * (32 * kk);
-            tile[r][c] = (co0 + r < e.Cout && c < ncol) ? e.w[((int64_t)(co0 + r) * e.Cin + ci0) * kk + c] : 0.f;
-        }
-        __syncthreads();
-        const int a = tid >> 5, l = tid & 31;
-        for (int t = 0; t < kk; ++t) {
-#pragma unroll
-            for (int rr = 0; rr < 32; rr += 8) {
-                const int r = rr + a;
-                if (e.w_fwd && co0 + r < e.Cout && ci0 + l < e.Cin) {
-                    const int64_t o = ((int64_t)t * e.Cout + co0 + r) * e.Cin + ci0 + l;
-                    const float v = tile[r][l * kk + t];
-                    if (bf) ((bf16_t*)e.w_fwd)[o] = (bf16_t)v; else ((float*)e.w_fwd)[o] = v;
-                }
-                if (e.w_dgrad && ci0 + r < e.Cin && co0 + l < e.Cout) {
-                    const float v = tile[l][r * kk + t];
-                    if (e.dgrad_paired) {
-                        const int64_t row = paired_row(t, ci0 + r, e.Cin);
-                        const int64_t o = row * e.Cout + co0 + l;
-                        if (bf) ((bf16_t*)e.w_dgrad)[o] = (bf16_t)v; else ((float*)e.w_dgrad)[o] = v;
-                        if (t % 3 == 0) {
-                            const int64_t z = (row - e.Cin) * e.Cout + co0 + l;
-                            if (bf) ((bf16_t*)e.w_dgrad)[z] = (bf16_t)0.f; else ((float*)e.w_dgrad)[z] = 0.f;
-                        }
-                    } else {
-                        const int64_t o = ((int64_t)t * e.Cin + ci0 + r) * e.Cout + co0 + l;
-                        if (bf) ((bf16_t*)e.w_dgrad)[o] = (bf16_t)v; else ((float*)e.w_dgrad)[o] = v;
-                    }
-                }
-            }
-        }
+        pack_tile_elementwise(e, tile, co0, ci0, tid);
     }
-    // zero pad tap (bf16 half-row k-tiles): taps_* may exceed k*k by one -- this tile's share of it
-    if (e.taps_fwd > kk || (!e.dgrad_paired && e.taps_dgrad > kk)) {
-        const int64_t cc = (int64_t)e.Cout * e.Cin;
-        for (int i = tid; i < 32 * 32; i += 256) {
-            const int r = i >> 5, c = i & 31;
-            if (co0 + r < e.Cout && ci0 + c < e.Cin) {
-                if (e.w_fwd && e.taps_fwd > kk) {
-                    const int64_t o = kk * cc + (int64_t)(co0 + r) * e.Cin + ci0 + c;
-                    if (bf) ((bf16_t*)e.w_fwd)[o] = (bf16_t)0.f; else ((float*)e.w_fwd)[o] = 0.f;
-                }
-                if (e.w_dgrad && !e.dgrad_paired && e.taps_dgrad > kk) {
-                    const int64_t o = kk * cc + (int64_t)(ci0 + c) * e.Cout + co0 + r;
-                    if (bf) ((bf16_t*)e.w_dgrad)[o] = (bf16_t)0.f; else ((float*)e.w_dgrad)[o] = 0.f;
-                }
-            }
-        }
-    }
+    pack_tile_pad_tap(e, co0, ci0, tid);
 }
 
 // Stride-2 dgrad of thin layers: the two output x-parities of a row are produced together as N' = 2*Cin columns (the
@@ -1926,6 +1894,103 @@ int packed_taps(const fva_conv_desc* d, int for_dgrad) {
     const int kk = d->ksize * d->ksize;
     const int C = for_dgrad ? d->Cout : d->Cin;
     return (halfrow_mode(d->dtype, C) && (kk & 1)) ? kk + 1 : kk;
+}
+
+// ---- launch plans: the launches a convolution is made of.  The entry points that launch walk them; the functions that size the
+// BatchNorm statistics tables (fva_conv_stat_blocks, fva_conv_dgrad_stat_rows) add up their rows.
+enum { LAUNCH_IGEMM, LAUNCH_PATCH1, LAUNCH_PATCH2 };   // implicit GEMM; patch kernel at stride 1 (PconvGeom); stride-2 dgrad patch kernel (Pdgrad2Geom)
+struct ConvLaunch {
+    int kind;
+    IgemmChoice igemm;          // LAUNCH_IGEMM: the kernel and its tile rows
+    int64_t M;                  // rows: the pixels of an OH x OW grid per image
+    int N, OH, OW;
+    int ntaps, tap_pix[MAX_TAPS], tap_w[MAX_TAPS];   // tap_w[ntaps]: the zero tap of the packed weights (finish_taps pads half-row k-tiles with it)
+    int ostep, ooy, oox;        // row (y, x) is output pixel (ostep * y + ooy, ostep * x + oox): 1 dense, 2 one parity class of a stride-2 dgrad
+    int row_blocks;             // blocks along M: cdiv(M, BM) of the kernel, or the patch kernel's tiles
+    int rows_per_block;         // statistics-table rows one of them owns: 2 in the paired form (two pixels' channels side by side)
+};
+
+void set_grid(ConvLaunch& e, int B, int OH, int OW, int N) {
+    e.M = (int64_t)B * OH * OW; e.N = N; e.OH = OH; e.OW = OW;
+    e.ntaps = 0; e.ostep = 1; e.ooy = e.oox = 0; e.rows_per_block = 1;
+}
+void add_tap(ConvLaunch& e, int pix, int w) { e.tap_pix[e.ntaps] = pix; e.tap_w[e.ntaps] = w; ++e.ntaps; }
+void close_taps(ConvLaunch& e, int zero_tap) { e.tap_w[e.ntaps] = zero_tap; }
+// picks the kernel for the e.ntaps taps; C: reduction channels, in_pixels: pixels of the halo input tensor plus one image (use_igemm8)
+void finish_igemm(ConvLaunch& e, int dtype, int C, int64_t in_pixels, bool head) {
+    e.kind = LAUNCH_IGEMM;
+    e.igemm = choose_igemm(dtype, e.M, e.N, C, e.ntaps, in_pixels, halfrow_mode(dtype, C), head);
+    e.row_blocks = cdiv(e.M, e.igemm.bm);
+}
+template <typename G>
+void finish_patch(ConvLaunch& e, int kind, const fva_conv_desc* d) {
+    e.kind = kind;
+    e.row_blocks = patch_tiles<G>(d->B, d->H, d->W);
+}
+
+// the forward launch of any epilogue; the patch kernel has the training forward (EPI_STATS) only
+ConvLaunch fwd_plan(const fva_conv_desc* d, int epi) {
+    const int k = d->ksize, s = d->stride, in_row = d->W + 2 * d->in_pad, in_img = (d->H + 2 * d->in_pad) * in_row;
+    ConvLaunch e;
+    set_grid(e, d->B, (d->H - 1) / s + 1, (d->W - 1) / s + 1, d->Cout);
+    if (k * k < MAX_TAPS) {
+        for (int kh = 0; kh < k; ++kh)
+            for (int kw = 0; kw < k; ++kw) add_tap(e, kh * in_row + kw, kh * k + kw);
+        close_taps(e, k * k);
+    } else {
+        e.ntaps = k * k;   // no kernel takes such a layer (check_desc); fva_conv_stat_blocks, which checks nothing, still counts its rows
+    }
+    finish_igemm(e, d->dtype, d->Cin, (int64_t)(d->B + 1) * in_img, epi == EPI_HEAD);
+    if (epi == EPI_STATS && use_pconv(d->dtype, k, s, d->Cin, d->Cout, d->H, d->W)) finish_patch<PconvGeom>(e, LAUNCH_PATCH1, d);
+    return e;
+}
+
+// Stride-2 3x3 dgrad, one axis: output pixels of parity 0 are reached through filter tap 1 alone, those of parity 1 through taps 0
+// and 2, tap 0 from the dy pixel one further on.
+int parity_taps(int parity, int kh[2], int off[2]) {
+    if (parity == 0) { kh[0] = 1; off[0] = 0; return 1; }
+    kh[0] = 0; off[0] = 1; kh[1] = 2; off[1] = 0;
+    return 2;
+}
+
+// the launches of the data gradient, in the order of their statistics rows; returns their number (at most 4)
+int dgrad_plan(const fva_conv_desc* d, ConvLaunch out[4]) {
+    const int k = d->ksize, s = d->stride, pd = k / 2, dtype = d->dtype;
+    const int OH = (d->H - 1) / s + 1, OW = (d->W - 1) / s + 1, in_row = OW + 2 * d->dy_pad;
+    const int64_t in_pixels = (int64_t)(d->B + 1) * (OH + 2 * d->dy_pad) * in_row;
+    ConvLaunch& e = out[0];
+    if (s == 1) {
+        set_grid(e, d->B, d->H, d->W, d->Cin);
+        for (int kh = 0; kh < k; ++kh)
+            for (int kw = 0; kw < k; ++kw) add_tap(e, (2 * pd - kh) * in_row + (2 * pd - kw), kh * k + kw);
+        close_taps(e, k * k);
+        finish_igemm(e, dtype, d->Cout, in_pixels, false);
+        if (use_pconv(dtype, k, s, d->Cout, d->Cin, d->H, d->W)) finish_patch<PconvGeom>(e, LAUNCH_PATCH1, d);
+        return 1;
+    }
+    if (use_pdgrad2(dtype, k, s, d->Cout, d->Cin)) {
+        set_grid(e, d->B, d->H, d->W, d->Cin);
+        finish_patch<Pdgrad2Geom>(e, LAUNCH_PATCH2, d);
+        return 1;
+    }
+    // Output-parity classes, each with its own tap subset (no wasted MACs): four launches -- or, for thin layers, both x-parities of
+    // an output row per launch (see dgrad_paired): two launches of N' = 2 * Cin columns over the virtual taps v = ky * 2 + dxo.
+    const bool paired = dgrad_paired(dtype, k, s, d->Cin, d->Cout);
+    int n = 0;
+    for (int py = 0; py < 2; ++py)
+        for (int px = 0; px < (paired ? 1 : 2); ++px) {
+            ConvLaunch& q = out[n++];
+            set_grid(q, d->B, d->H / 2, d->W / 2, paired ? 2 * d->Cin : d->Cin);
+            int ky[2], yo[2], kx[2] = {0, 1}, xo[2] = {0, 1};   // paired: along x the virtual taps dxo = 0, 1
+            const int ny = parity_taps(py, ky, yo), nx = paired ? 2 : parity_taps(px, kx, xo);
+            for (int a = 0; a < ny; ++a)
+                for (int b = 0; b < nx; ++b) add_tap(q, (d->dy_pad + yo[a]) * in_row + d->dy_pad + xo[b], ky[a] * (paired ? 2 : 3) + kx[b]);
+            q.ostep = 2; q.ooy = py; q.oox = px;
+            q.rows_per_block = paired ? 2 : 1;
+            close_taps(q, paired ? 0 : 9);
+            finish_igemm(q, dtype, d->Cout, in_pixels, false);
+        }
+    return n;
 }
 
 }  // namespace
@@ -1985,80 +2050,85 @@ int fva_conv_pack_weights_tiled(const fva_pack_entry* table_dev, int32_t n, int3
 
 int32_t fva_conv_stat_blocks(const fva_conv_desc* d) {
     if (!d) return 0;
-    if (use_pconv(d->dtype, d->ksize, d->stride, d->Cin, d->Cout, d->H, d->W)) return patch_tiles<PconvGeom>(d->B, d->H, d->W);
-    const int OH = (d->H - 1) / d->stride + 1, OW = (d->W - 1) / d->stride + 1;
-    const int64_t M = (int64_t)d->B * OH * OW;
-    const int64_t in_img = (int64_t)(d->H + 2 * d->in_pad) * (d->W + 2 * d->in_pad);
-    if (!halfrow_mode(d->dtype, d->Cin) && use_igemm8(d->dtype, M, d->Cout, d->Cin, d->ksize * d->ksize, (M / ((int64_t)OH * OW) + 1) * in_img))
-        return cdiv(M, 256);
-    return cdiv(M, tile_bm(d->dtype, (int)M, d->Cout));
+    return fwd_plan(d, EPI_STATS).row_blocks;
 }
 
-static int setup_fwd(const fva_conv_desc* d, IgemmParams& p, const char* who) {
+// the launch's grid, columns and taps -> kernel parameters (p.C and the input geometry are set)
+static void set_launch(IgemmParams& p, const ConvLaunch& e, int dtype) {
+    p.M = (int)e.M;
+    p.N = e.N;
+    p.OW = e.OW;
+    p.OHW = e.OH * e.OW;
+    p.div_ow = make_fastdiv(p.OW);
+    p.div_ohw = make_fastdiv(p.OHW);
+    for (int t = 0; t < e.ntaps; ++t) {
+        p.tap_pix[t] = e.tap_pix[t];
+        p.tap_w[t] = e.tap_w[t];
+    }
+    p.tap_w[e.ntaps] = e.tap_w[e.ntaps];  // zero tap (present in packed weights when needed)
+    finish_taps(p, e.ntaps, dtype);
+    p.out_dense = e.ostep == 1 ? 1 : 0;
+    if (!p.out_dense) {
+        p.osy = p.osx = e.ostep;
+        p.ooy = e.ooy;
+        p.oox = e.oox;
+    }
+}
+
+static int setup_fwd(const fva_conv_desc* d, int epi, IgemmParams& p, ConvLaunch& e, const char* who) {
     int rc = check_desc(d, who);
     if (rc) return rc;
     rc = check_red_channels(d->dtype, d->Cin, who);
     if (rc) return rc;
-    const int k = d->ksize, s = d->stride;
-    const int OH = (d->H - 1) / s + 1, OW = (d->W - 1) / s + 1;
+    e = fwd_plan(d, epi);
     p = IgemmParams();
     p.acc_rep = p.bnb_rep = p.ax_rep = 1;
-    p.M = d->B * OH * OW;
-    p.N = d->Cout;
     p.C = d->Cin;
-    p.OW = OW;
-    p.OHW = OH * OW;
-    p.div_ow = make_fastdiv(OW);
-    p.div_ohw = make_fastdiv(OH * OW);
     p.in_row = d->W + 2 * d->in_pad;
     p.in_img = (d->H + 2 * d->in_pad) * p.in_row;
-    p.sy = p.sx = s;
-    p.y0 = p.x0 = d->in_pad - k / 2;
-    int nt = 0;
-    for (int kh = 0; kh < k; ++kh)
-        for (int kw = 0; kw < k; ++kw) {
-            p.tap_pix[nt] = kh * p.in_row + kw;
-            p.tap_w[nt] = kh * k + kw;
-            ++nt;
-        }
-    p.tap_w[nt] = k * k;  // zero tap (present in packed weights when needed)
-    finish_taps(p, nt, d->dtype);
-    p.out_dense = 1;
+    p.sy = p.sx = d->stride;
+    p.y0 = p.x0 = d->in_pad - d->ksize / 2;
+    set_launch(p, e, d->dtype);
     p.out_pitch = d->Cout;
     return FVA_OK;
 }
 
-int fva_conv_fwd(const fva_conv_desc* d, const void* x, const void* w_fwd, void* y, float* stats_partial, void* stream) {
+// fva_conv_fwd (statistics into the table stats_partial) and fva_conv_fwd_acc (with_acc: into the accumulator acc)
+static int conv_fwd_impl(const char* who, const fva_conv_desc* d, const void* x, const void* w_fwd, void* y, float* stats_partial, bool with_acc,
+                         int64_t* acc, int32_t replicas, void* stream) {
     IgemmParams p;
-    int rc = setup_fwd(d, p, "fva_conv_fwd");
+    ConvLaunch e;
+    int rc = setup_fwd(d, EPI_STATS, p, e, who);
     if (rc) return rc;
-    if (!x || !w_fwd || !y) return fva_fail(FVA_ERR_ARG, "fva_conv_fwd: null pointer");
-    if (d->Cout % 8) return fva_fail(FVA_ERR_ARG, "fva_conv_fwd: Cout %d not a multiple of 8", d->Cout);
+    if (!x || !w_fwd || !y || (with_acc && !acc)) return fva_fail(FVA_ERR_ARG, "%s: null pointer", who);
+    if (with_acc && !fva_replicas_ok(replicas)) return fva_fail(FVA_ERR_ARG, "%s: replicas = %d is not a power of two in 1..%d", who, replicas, FVA_BN_ACC_MAX_REPLICAS);
+    if (d->Cout % 8) return fva_fail(FVA_ERR_ARG, "%s: Cout %d not a multiple of 8", who, d->Cout);
     p.in = x;
     p.wt = w_fwd;
     p.out = y;
     p.stats = stats_partial;
+    p.stats_acc = (long long*)acc;
+    p.acc_rep = replicas;
     FvaProfileSpan span(0 | (d->ksize << 8), 2.0 * p.M * (double)d->Cout * d->Cin * d->ksize * d->ksize, (hipStream_t)stream);
-    if (use_pconv(d->dtype, d->ksize, d->stride, d->Cin, d->Cout, d->H, d->W)) return launch_patch<PconvGeom, EPI_STATS>(p, d->B, d->H, d->W, false, (hipStream_t)stream);
-    return launch_igemm<EPI_STATS>(d->dtype, p, (hipStream_t)stream);
+    if (e.kind == LAUNCH_PATCH1) return launch_patch<PconvGeom, EPI_STATS>(p, d->B, d->H, d->W, false, (hipStream_t)stream);
+    return launch_igemm<EPI_STATS>(e.igemm, d->dtype, p, (hipStream_t)stream);
+}
+
+int fva_conv_fwd(const fva_conv_desc* d, const void* x, const void* w_fwd, void* y, float* stats_partial, void* stream) {
+    return conv_fwd_impl("fva_conv_fwd", d, x, w_fwd, y, stats_partial, false, nullptr, 1, stream);
+}
+
+int fva_conv_fwd_acc(const fva_conv_desc* d, const void* x, const void* w_fwd, void* y, int64_t* acc, int32_t replicas, void* stream) {
+    return conv_fwd_impl("fva_conv_fwd_acc", d, x, w_fwd, y, nullptr, true, acc, replicas, stream);
 }
 
 /* The forward apply pass of the block BEFORE a 1x1 convolution, fused into that convolution (igemm_kernel<..., AX>): see the header. */
 static int conv1x1_fwd_apply_impl(const fva_conv_desc* d, const void* y_prev, const float* scale, const float* shift, const fva_bn_fwd_acc* prev,
                                   const void* residual, int32_t res_pad, void* z, const void* w_fwd, void* y, float* stats_partial,
-                                  int64_t* acc_out, int32_t replicas_out, void* stream);
-
-int fva_conv1x1_fwd_apply(const fva_conv_desc* d, const void* y_prev, const float* scale, const float* shift, const void* residual,
-                          int32_t res_pad, void* z, const void* w_fwd, void* y, float* stats_partial, void* stream) {
-    if (!scale || !shift) return fva_fail(FVA_ERR_ARG, "fva_conv1x1_fwd_apply: null pointer");
-    return conv1x1_fwd_apply_impl(d, y_prev, scale, shift, nullptr, residual, res_pad, z, w_fwd, y, stats_partial, nullptr, 1, stream);
-}
-
-static int conv1x1_fwd_apply_impl(const fva_conv_desc* d, const void* y_prev, const float* scale, const float* shift, const fva_bn_fwd_acc* prev,
-                                  const void* residual, int32_t res_pad, void* z, const void* w_fwd, void* y, float* stats_partial,
                                   int64_t* acc_out, int32_t replicas_out, void* stream) {
     IgemmParams p;
-    int rc = setup_fwd(d, p, "fva_conv1x1_fwd_apply");
+    ConvLaunch e;
+    int rc = setup_fwd(d, EPI_STATS, p, e, "fva_conv1x1_fwd_apply");
     if (rc) return rc;
     if (!y_prev || !z || !w_fwd || !y) return fva_fail(FVA_ERR_ARG, "fva_conv1x1_fwd_apply: null pointer");
     if (d->dtype != FVA_BF16 || d->ksize != 1 || d->stride != 1) return fva_fail(FVA_ERR_ARG, "fva_conv1x1_fwd_apply: a bf16 1x1 stride-1 layer only");
@@ -2087,21 +2157,10 @@ static int conv1x1_fwd_apply_impl(const fva_conv_desc* d, const void* y_prev, co
                           : launch_one<bf16_t, 256, 64, EPI_STATS, 2, true>(p, (hipStream_t)stream);
 }
 
-int fva_conv_fwd_acc(const fva_conv_desc* d, const void* x, const void* w_fwd, void* y, int64_t* acc, int32_t replicas, void* stream) {
-    IgemmParams p;
-    int rc = setup_fwd(d, p, "fva_conv_fwd_acc");
-    if (rc) return rc;
-    if (!x || !w_fwd || !y || !acc) return fva_fail(FVA_ERR_ARG, "fva_conv_fwd_acc: null pointer");
-    if (!fva_replicas_ok(replicas)) return fva_fail(FVA_ERR_ARG, "fva_conv_fwd_acc: replicas = %d is not a power of two in 1..%d", replicas, FVA_BN_ACC_MAX_REPLICAS);
-    if (d->Cout % 8) return fva_fail(FVA_ERR_ARG, "fva_conv_fwd_acc: Cout %d not a multiple of 8", d->Cout);
-    p.in = x;
-    p.wt = w_fwd;
-    p.out = y;
-    p.stats_acc = (long long*)acc;
-    p.acc_rep = replicas;
-    FvaProfileSpan span(0 | (d->ksize << 8), 2.0 * p.M * (double)d->Cout * d->Cin * d->ksize * d->ksize, (hipStream_t)stream);
-    if (use_pconv(d->dtype, d->ksize, d->stride, d->Cin, d->Cout, d->H, d->W)) return launch_patch<PconvGeom, EPI_STATS>(p, d->B, d->H, d->W, false, (hipStream_t)stream);
-    return launch_igemm<EPI_STATS>(d->dtype, p, (hipStream_t)stream);
+int fva_conv1x1_fwd_apply(const fva_conv_desc* d, const void* y_prev, const float* scale, const float* shift, const void* residual,
+                          int32_t res_pad, void* z, const void* w_fwd, void* y, float* stats_partial, void* stream) {
+    if (!scale || !shift) return fva_fail(FVA_ERR_ARG, "fva_conv1x1_fwd_apply: null pointer");
+    return conv1x1_fwd_apply_impl(d, y_prev, scale, shift, nullptr, residual, res_pad, z, w_fwd, y, stats_partial, nullptr, 1, stream);
 }
 
 int fva_conv1x1_fwd_apply_acc(const fva_conv_desc* d, const void* y_prev, const fva_bn_fwd_acc* prev, const void* residual, int32_t res_pad,
@@ -2122,60 +2181,48 @@ int fva_conv1x1_fwd_apply_acc(const fva_conv_desc* d, const void* y_prev, const 
     return conv1x1_fwd_apply_impl(d, y_prev, nullptr, nullptr, prev, residual, res_pad, z, w_fwd, y, nullptr, acc_out, replicas_out, stream);
 }
 
-int fva_conv_fwd_bnact(const fva_conv_desc* d, const void* x, const void* w_fwd, const float* scale, const float* shift,
-                       const void* residual, void* z, int32_t z_pad, void* stream) {
+// fva_conv_fwd_bnact (SiLU(acc * scale + shift) + residual) and fva_conv_fwd_bias_act (bias_form: act(acc + shift), no scale, no residual)
+static int conv_fwd_act_impl(const char* who, bool bias_form, const fva_conv_desc* d, const void* x, const void* w_fwd, const float* scale,
+                             const float* shift, int32_t act, const void* residual, void* z, int32_t z_pad, void* stream) {
     IgemmParams p;
-    int rc = setup_fwd(d, p, "fva_conv_fwd_bnact");
+    ConvLaunch e;
+    int rc = setup_fwd(d, EPI_BNACT, p, e, who);
     if (rc) return rc;
-    if (!x || !w_fwd || !scale || !shift || !z) return fva_fail(FVA_ERR_ARG, "fva_conv_fwd_bnact: null pointer");
-    if (d->Cout % 8 || z_pad < 0) return fva_fail(FVA_ERR_ARG, "fva_conv_fwd_bnact: Cout %d not a multiple of 8 or bad z_pad", d->Cout);
-    const int OH = (d->H - 1) / d->stride + 1, OW = (d->W - 1) / d->stride + 1;
+    if (!x || !w_fwd || (!bias_form && !scale) || !shift || !z) return fva_fail(FVA_ERR_ARG, "%s: null pointer", who);
+    if (d->Cout % 8 || z_pad < 0 || (bias_form && (act < 1 || act > 2)))
+        return fva_fail(FVA_ERR_ARG, bias_form ? "%s: Cout %d not a multiple of 8, bad z_pad or act" : "%s: Cout %d not a multiple of 8 or bad z_pad", who, d->Cout);
     p.in = x;
     p.wt = w_fwd;
     p.out = z;
     p.scale = scale;
     p.shift = shift;
+    p.act = act;
     p.addend = residual;          // same halo geometry as z
     p.out_dense = 0;
-    p.out_row = OW + 2 * z_pad;
-    p.out_img = (OH + 2 * z_pad) * p.out_row;
+    p.out_row = e.OW + 2 * z_pad;
+    p.out_img = (e.OH + 2 * z_pad) * p.out_row;
     p.osy = p.osx = 1;
     p.ooy = p.oox = z_pad;
     FvaProfileSpan span(0 | (d->ksize << 8), 2.0 * p.M * (double)d->Cout * d->Cin * d->ksize * d->ksize, (hipStream_t)stream);
-    rc = launch_igemm<EPI_BNACT>(d->dtype, p, (hipStream_t)stream);
+    rc = launch_igemm<EPI_BNACT>(e.igemm, d->dtype, p, (hipStream_t)stream);
     if (rc || z_pad == 0) return rc;
-    return fva_zero_halo_border(z, d->B, OH, OW, d->Cout * (d->dtype == FVA_BF16 ? 2 : 4) / 16, z_pad, (hipStream_t)stream);
+    return fva_zero_halo_border(z, d->B, e.OH, e.OW, d->Cout * (d->dtype == FVA_BF16 ? 2 : 4) / 16, z_pad, (hipStream_t)stream);
+}
+
+int fva_conv_fwd_bnact(const fva_conv_desc* d, const void* x, const void* w_fwd, const float* scale, const float* shift,
+                       const void* residual, void* z, int32_t z_pad, void* stream) {
+    return conv_fwd_act_impl("fva_conv_fwd_bnact", false, d, x, w_fwd, scale, shift, 0, residual, z, z_pad, stream);
 }
 
 int fva_conv_fwd_bias_act(const fva_conv_desc* d, const void* x, const void* w_fwd, const float* bias, int32_t act, void* z, int32_t z_pad,
                           void* stream) {
-    IgemmParams p;
-    int rc = setup_fwd(d, p, "fva_conv_fwd_bias_act");
-    if (rc) return rc;
-    if (!x || !w_fwd || !bias || !z) return fva_fail(FVA_ERR_ARG, "fva_conv_fwd_bias_act: null pointer");
-    if (d->Cout % 8 || z_pad < 0 || act < 1 || act > 2) return fva_fail(FVA_ERR_ARG, "fva_conv_fwd_bias_act: Cout %d not a multiple of 8, bad z_pad or act", d->Cout);
-    const int OH = (d->H - 1) / d->stride + 1, OW = (d->W - 1) / d->stride + 1;
-    p.in = x;
-    p.wt = w_fwd;
-    p.out = z;
-    p.scale = nullptr;
-    p.shift = bias;
-    p.act = act;
-    p.addend = nullptr;
-    p.out_dense = 0;
-    p.out_row = OW + 2 * z_pad;
-    p.out_img = (OH + 2 * z_pad) * p.out_row;
-    p.osy = p.osx = 1;
-    p.ooy = p.oox = z_pad;
-    FvaProfileSpan span(0 | (d->ksize << 8), 2.0 * p.M * (double)d->Cout * d->Cin * d->ksize * d->ksize, (hipStream_t)stream);
-    rc = launch_igemm<EPI_BNACT>(d->dtype, p, (hipStream_t)stream);
-    if (rc || z_pad == 0) return rc;
-    return fva_zero_halo_border(z, d->B, OH, OW, d->Cout * (d->dtype == FVA_BF16 ? 2 : 4) / 16, z_pad, (hipStream_t)stream);
+    return conv_fwd_act_impl("fva_conv_fwd_bias_act", true, d, x, w_fwd, nullptr, bias, act, nullptr, z, z_pad, stream);
 }
 
 int fva_head_fwd(const fva_conv_desc* d, const void* x, const void* w_fwd, const float* bias, float* out, void* stream) {
     IgemmParams p;
-    int rc = setup_fwd(d, p, "fva_head_fwd");
+    ConvLaunch e;
+    int rc = setup_fwd(d, EPI_HEAD, p, e, "fva_head_fwd");
     if (rc) return rc;
     if (d->ksize != 1) return fva_fail(FVA_ERR_ARG, "fva_head_fwd: ksize must be 1");
     if (!x || !w_fwd || !bias || !out) return fva_fail(FVA_ERR_ARG, "fva_head_fwd: null pointer");
@@ -2184,32 +2231,14 @@ int fva_head_fwd(const fva_conv_desc* d, const void* x, const void* w_fwd, const
     p.out = out;
     p.bias = bias;
     FvaProfileSpan span(0 | (d->ksize << 8), 2.0 * p.M * (double)d->Cout * d->Cin * d->ksize * d->ksize, (hipStream_t)stream);
-    return launch_igemm<EPI_HEAD>(d->dtype, p, (hipStream_t)stream);
-}
-
-// row blocks (BM of the tile the dispatcher picks) of ONE dgrad launch with m rows, n columns, reduction over c channels x ntaps
-static int dgrad_launch_rows(const fva_conv_desc* d, int64_t m, int n, int c, int ntaps, int64_t in_pixels) {
-    if (!halfrow_mode(d->dtype, c) && use_igemm8(d->dtype, m, n, c, ntaps, in_pixels)) return cdiv(m, 256);
-    return cdiv(m, tile_bm(d->dtype, (int)m, n));
+    return launch_igemm<EPI_HEAD>(e.igemm, d->dtype, p, (hipStream_t)stream);
 }
 
 int32_t fva_conv_dgrad_stat_rows(const fva_conv_desc* d) {
     if (!d || check_desc(d, "fva_conv_dgrad_stat_rows")) return 0;
-    const int k = d->ksize, s = d->stride;
-    const int OH = (d->H - 1) / s + 1, OW = (d->W - 1) / s + 1;
-    const int64_t in_pixels = (int64_t)(d->B + 1) * (OH + 2 * d->dy_pad) * (OW + 2 * d->dy_pad);
-    if (use_pconv(d->dtype, k, s, d->Cout, d->Cin, d->H, d->W)) return patch_tiles<PconvGeom>(d->B, d->H, d->W);
-    if (s == 1) return dgrad_launch_rows(d, (int64_t)d->B * d->H * d->W, d->Cin, d->Cout, k * k, in_pixels);
-    const int64_t mq = (int64_t)d->B * (d->H / 2) * (d->W / 2);
-    if (use_pdgrad2(d->dtype, k, s, d->Cout, d->Cin)) return patch_tiles<Pdgrad2Geom>(d->B, d->H, d->W);
-    if (dgrad_paired(d->dtype, k, s, d->Cin, d->Cout)) {   // two launches (row parity) of N' = 2 * Cin columns: two table rows per block
-        int rows = 0;
-        for (int py = 0; py < 2; ++py) rows += 2 * dgrad_launch_rows(d, mq, 2 * d->Cin, d->Cout, py == 0 ? 2 : 4, in_pixels);
-        return rows;
-    }
+    ConvLaunch plan[4];
     int rows = 0;
-    for (int py = 0; py < 2; ++py)
-        for (int px = 0; px < 2; ++px) rows += dgrad_launch_rows(d, mq, d->Cin, d->Cout, (py ? 2 : 1) * (px ? 2 : 1), in_pixels);
+    for (int i = 0, n = dgrad_plan(d, plan); i < n; ++i) rows += plan[i].row_blocks * plan[i].rows_per_block;
     return rows;
 }
 
@@ -2228,7 +2257,8 @@ int fva_conv_dgrad_bnstats(const fva_conv_desc* d, const void* dy, const void* w
     const int k = d->ksize, s = d->stride, pd = k / 2;
     if (d->dy_pad < pd) return fva_fail(FVA_ERR_ARG, "fva_conv_dgrad: dy_pad %d < %d", d->dy_pad, pd);
     const int OH = (d->H - 1) / s + 1, OW = (d->W - 1) / s + 1;
-    FvaProfileSpan span(1 | (k << 8), 2.0 * d->B * OH * OW * (double)d->Cout * d->Cin * k * k, (hipStream_t)stream);
+    hipStream_t st = (hipStream_t)stream;
+    FvaProfileSpan span(1 | (k << 8), 2.0 * d->B * OH * OW * (double)d->Cout * d->Cin * k * k, st);
     IgemmParams p = IgemmParams();
     p.acc_rep = p.bnb_rep = p.ax_rep = 1;
     p.in = dy;
@@ -2251,102 +2281,29 @@ int fva_conv_dgrad_bnstats(const fva_conv_desc* d, const void* dy, const void* w
         p.bnb_row0 = 0;
         p.bnb_C = d->Cin;
     }
-    const int64_t in_pixels = (int64_t)(d->B + 1) * (OH + 2 * d->dy_pad) * (OW + 2 * d->dy_pad);
-    if (s == 1) {
-        p.M = d->B * d->H * d->W;
-        p.OW = d->W;
-        p.OHW = d->H * d->W;
-        p.div_ow = make_fastdiv(p.OW);
-        p.div_ohw = make_fastdiv(p.OHW);
-        p.y0 = p.x0 = d->dy_pad - pd;
-        int nt = 0;
-        for (int kh = 0; kh < k; ++kh)
-            for (int kw = 0; kw < k; ++kw) {
-                p.tap_pix[nt] = (2 * pd - kh) * p.in_row + (2 * pd - kw);
-                p.tap_w[nt] = kh * k + kw;
-                ++nt;
+    ConvLaunch plan[4];
+    for (int i = 0, n = dgrad_plan(d, plan); i < n; ++i) {
+        const ConvLaunch& e = plan[i];
+        if (e.kind == LAUNCH_PATCH2) {        // the kernel walks the dx image itself: no row grid, no tap list
+            p.y0 = p.x0 = d->dy_pad;          // dy pixel (i, j) sits at padded (i + pad, j + pad); rows / columns up to OH / OW are the zero halo
+            p.out_dense = 1;
+            rc = f ? launch_patch<Pdgrad2Geom, EPI_BNB>(p, d->B, d->H, d->W, false, st) : launch_patch<Pdgrad2Geom, EPI_PLAIN>(p, d->B, d->H, d->W, false, st);
+        } else {
+            p.y0 = p.x0 = e.ostep == 1 ? d->dy_pad - pd : 0;
+            if (e.ostep == 2) {
+                p.out_img = d->H * d->W;
+                p.out_row = d->W;
             }
-        p.tap_w[nt] = k * k;
-        finish_taps(p, nt, d->dtype);
-        p.out_dense = 1;
-        if (use_pconv(d->dtype, k, s, d->Cout, d->Cin, d->H, d->W))
-            return f ? launch_patch<PconvGeom, EPI_BNB>(p, d->B, d->H, d->W, true, (hipStream_t)stream) : launch_patch<PconvGeom, EPI_PLAIN>(p, d->B, d->H, d->W, true, (hipStream_t)stream);
-        return f ? launch_igemm<EPI_BNB>(d->dtype, p, (hipStream_t)stream) : launch_igemm<EPI_PLAIN>(d->dtype, p, (hipStream_t)stream);
-    }
-    const int JH = d->H / 2, JW = d->W / 2;
-    if (use_pdgrad2(d->dtype, k, s, d->Cout, d->Cin)) {
-        p.y0 = p.x0 = d->dy_pad;          // dy pixel (i, j) sits at padded (i + pad, j + pad); rows / columns up to OH / OW are the zero halo
-        p.out_dense = 1;
-        return f ? launch_patch<Pdgrad2Geom, EPI_BNB>(p, d->B, d->H, d->W, false, (hipStream_t)stream) : launch_patch<Pdgrad2Geom, EPI_PLAIN>(p, d->B, d->H, d->W, false, (hipStream_t)stream);
-    }
-    if (dgrad_paired(d->dtype, k, s, d->Cin, d->Cout)) {
-        // thin layers: both x-parities of an output row per launch (see dgrad_paired) -- 2 launches, N' = 2*Cin
-        p.M = d->B * JH * JW;
-        p.N = 2 * d->Cin;
-        p.OW = JW;
-        p.OHW = JH * JW;
-        p.div_ow = make_fastdiv(p.OW);
-        p.div_ohw = make_fastdiv(p.OHW);
-        p.y0 = p.x0 = 0;
-        p.out_dense = 0;
-        p.out_img = d->H * d->W;
-        p.out_row = d->W;
-        p.osy = p.osx = 2;
-        p.oox = 0;
-        for (int py = 0; py < 2; ++py) {
-            int nt = 0;
-            const int nky = py == 0 ? 1 : 2;
-            const int kys[2] = {py == 0 ? 1 : 0, 2};
-            const int yos[2] = {py == 0 ? d->dy_pad : d->dy_pad + 1, d->dy_pad};
-            for (int a = 0; a < nky; ++a)
-                for (int dxo = 0; dxo < 2; ++dxo) {
-                    p.tap_pix[nt] = yos[a] * p.in_row + d->dy_pad + dxo;
-                    p.tap_w[nt] = kys[a] * 2 + dxo;
-                    ++nt;
-                }
-            p.tap_w[nt] = 0;
-            finish_taps(p, nt, d->dtype);
-            if (p.halfrow) return fva_fail(FVA_ERR_ARG, "fva_conv_dgrad: paired stride-2 path needs Cout >= 64");
-            p.ooy = py;
-            rc = f ? launch_igemm<EPI_BNB>(d->dtype, p, (hipStream_t)stream) : launch_igemm<EPI_PLAIN>(d->dtype, p, (hipStream_t)stream);
-            if (rc) return rc;
-            p.bnb_row0 += dgrad_launch_rows(d, p.M, p.N, p.C, nt, in_pixels);
+            set_launch(p, e, d->dtype);
+            if (e.rows_per_block == 2 && p.halfrow) return fva_fail(FVA_ERR_ARG, "fva_conv_dgrad: paired stride-2 path needs Cout >= 64");
+            if (e.kind == LAUNCH_PATCH1) rc = f ? launch_patch<PconvGeom, EPI_BNB>(p, d->B, d->H, d->W, true, st) : launch_patch<PconvGeom, EPI_PLAIN>(p, d->B, d->H, d->W, true, st);
+            else rc = f ? launch_igemm<EPI_BNB>(e.igemm, d->dtype, p, st) : launch_igemm<EPI_PLAIN>(e.igemm, d->dtype, p, st);
         }
-        return FVA_OK;
+        if (rc) return rc;
+        // bnb_row0 counts row BLOCKS, not table rows: the kernel writes rows (bnb_row0 + mblk) * rows_per_block + {0, 1} (bnb_finish), so a
+        // paired launch advances the table by twice its blocks -- what fva_conv_dgrad_stat_rows adds up
+        p.bnb_row0 += e.row_blocks;
     }
-    // stride 2, 3x3: four output-parity classes, each with its own tap subset (no wasted MACs)
-    p.M = d->B * JH * JW;
-    p.OW = JW;
-    p.OHW = JH * JW;
-    p.div_ow = make_fastdiv(p.OW);
-    p.div_ohw = make_fastdiv(p.OHW);
-    p.y0 = p.x0 = 0;
-    p.out_dense = 0;
-    p.out_img = d->H * d->W;
-    p.out_row = d->W;
-    p.osy = p.osx = 2;
-    for (int py = 0; py < 2; ++py)
-        for (int px = 0; px < 2; ++px) {
-            int khs[2], yo[2], nky, kws[2], xo[2], nkx;
-            if (py == 0) { nky = 1; khs[0] = 1; yo[0] = d->dy_pad; }
-            else { nky = 2; khs[0] = 0; yo[0] = d->dy_pad + 1; khs[1] = 2; yo[1] = d->dy_pad; }
-            if (px == 0) { nkx = 1; kws[0] = 1; xo[0] = d->dy_pad; }
-            else { nkx = 2; kws[0] = 0; xo[0] = d->dy_pad + 1; kws[1] = 2; xo[1] = d->dy_pad; }
-            int nt = 0;
-            for (int a = 0; a < nky; ++a)
-                for (int b = 0; b < nkx; ++b) {
-                    p.tap_pix[nt] = yo[a] * p.in_row + xo[b];
-                    p.tap_w[nt] = khs[a] * 3 + kws[b];
-                    ++nt;
-                }
-            p.tap_w[nt] = 9;
-            finish_taps(p, nt, d->dtype);
-            p.ooy = py;
-            p.oox = px;
-            rc = f ? launch_igemm<EPI_BNB>(d->dtype, p, (hipStream_t)stream) : launch_igemm<EPI_PLAIN>(d->dtype, p, (hipStream_t)stream);
-            if (rc) return rc;
-            p.bnb_row0 += dgrad_launch_rows(d, p.M, p.N, p.C, nt, in_pixels);
-        }
     return FVA_OK;
 }
 

@@ -69,17 +69,19 @@ def test_dgrad_bnstats_equals_reduce_pass(case, key, with_addend):
 
     rows = lib.fva_conv_dgrad_stat_rows(C.byref(d))
     assert rows > 0
-    part = torch.full((lib.fva_bn_partial_rows(rows), 2, Cin), float('nan'), device=DEV)
+    GUARD = 8                                   # rows behind the table (fva_bn_partial_rows(rows) is rows itself below 1024): nobody may write them
+    part = torch.full((lib.fva_bn_partial_rows(rows) + GUARD, 2, Cin), float('nan'), device=DEV)
     fs = _lib.BnBwdFuse(y.data_ptr(), scale.data_ptr(), shift.data_ptr(), mean.data_ptr(), rstd.data_ptr(), part.data_ptr())
     dx1 = torch.empty_like(dx0)
     _lib.call('fva_conv_dgrad_bnstats', C.byref(d), C.c_void_p(dyptr), ops._p(wd), ops._p(dx1), ops._p(add), C.byref(fs), ops._stream())
     assert torch.equal(dx0, dx1), 'the fused launch must store exactly what the plain dgrad stores'
     assert torch.isfinite(part[:rows]).all(), 'every row of the partial table is written'
+    assert part[rows:].shape[0] >= GUARD and torch.isnan(part[rows:]).all(), 'no launch writes behind the rows that fva_conv_dgrad_stat_rows counts'
 
     def finalize(table, nb):
         dg, db = torch.empty(Cin, device=DEV), torch.empty(Cin, device=DEV)
         coef = torch.empty((3, Cin), device=DEV)
-        _lib.call('fva_bn_bwd_finalize', ops._p(table), nb, table.shape[0], M, Cin, ops._p(gamma), ops._p(rstd), ops._p(dg), ops._p(db), 0, ops._p(coef),
+        _lib.call('fva_bn_bwd_finalize', ops._p(table), nb, lib.fva_bn_partial_rows(nb), M, Cin, ops._p(gamma), ops._p(rstd), ops._p(dg), ops._p(db), 0, ops._p(coef),
                   ops._stream())
         return dg, db, coef
     dg1, db1, coef1 = finalize(part, rows)

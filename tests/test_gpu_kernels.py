@@ -245,13 +245,18 @@ def test_multi_tensor_weight_pack_matches_single(key):
     from fastvision_amd import _lib, ops
     dtype = DT[key]
     lib = _lib.load()
-    shapes = [(64, 32, 3), (32, 64, 1), (255, 128, 1), (128, 64, 3), (48, 40, 3), (256, 128, 3), (64, 128, 3)]
+    shapes = [(64, 32, 3, 1), (32, 64, 1, 1), (255, 128, 1, 1), (128, 64, 3, 1), (48, 40, 3, 1), (256, 128, 3, 1), (64, 128, 3, 1),
+              # stride 2: the paired dgrad layout [6][2 Cin][Cout] with its zero halves (thin layers that the stride-2 patch kernel does not take)
+              (64, 64, 3, 2),       # paired in both dtypes, whole tiles
+              (64, 32, 3, 2),       # paired in fp32; pad tap and plain layout in bf16
+              (48, 40, 3, 2),       # paired, ragged both ways
+              (128, 64, 3, 2)]      # paired in fp32
     g = torch.Generator().manual_seed(9)
-    ws = [torch.randn(co, ci, k, k, generator=g).to(dev()) for co, ci, k in shapes]
+    ws = [torch.randn(co, ci, k, k, generator=g).to(dev()) for co, ci, k, _ in shapes]
     arr = (_lib.PackEntry * len(ws))()
     singles, multis, mx = [], [], 0
-    for i, (w, (co, ci, k)) in enumerate(zip(ws, shapes)):
-        d = _lib.ConvDesc(ops._code(dtype), 1, 8, 8, ci, co, k, 1, 1, 1)
+    for i, (w, (co, ci, k, st)) in enumerate(zip(ws, shapes)):
+        d = _lib.ConvDesc(ops._code(dtype), 1, 8, 8, ci, co, k, st, 1, 1)
         singles.append(ops.packed_weights(w, d, dtype, cache=False))
         wf = torch.full((lib.fva_conv_packed_elems(C.byref(d), 0),), float('nan'), dtype=dtype, device=dev())
         wd = torch.full((lib.fva_conv_packed_elems(C.byref(d), 1),), float('nan'), dtype=dtype, device=dev())
@@ -260,6 +265,7 @@ def test_multi_tensor_weight_pack_matches_single(key):
         e.w, e.w_fwd, e.w_dgrad = w.data_ptr(), wf.data_ptr(), wd.data_ptr()
         e.Cout, e.Cin, e.ksize, e.dtype = co, ci, k, ops._code(dtype)
         e.taps_fwd, e.taps_dgrad = wf.numel() // (co * ci), wd.numel() // (co * ci)
+        e.dgrad_paired = 1 if (st == 2 and e.taps_dgrad == 12) else 0      # as ops._PackRegistry sets it
         mx = max(mx, wf.numel(), wd.numel())
     table = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev())
     _lib.call('fva_conv_pack_weights_multi', ops._p(table), len(ws), mx, ops._stream())
@@ -269,7 +275,7 @@ def test_multi_tensor_weight_pack_matches_single(key):
     for mf, md in multis:
         mf.fill_(float('nan')); md.fill_(float('nan'))
     tiles = 0
-    for i, (co, ci, k) in enumerate(shapes):
+    for i, (co, ci, k, _) in enumerate(shapes):
         arr[i].tile_start = tiles
         tiles += ((co + 31) // 32) * ((ci + 31) // 32)
     table = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev())
