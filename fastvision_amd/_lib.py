@@ -158,6 +158,8 @@ PROTOTYPES = {
     'fva_sgd_chunk_elems': (_I, []),
     'fva_sgd_clip_coef': (_I, [_P, _I, _P, _I, _P, C.c_double, _P, _P]),
     'fva_sgd_step': (_I, [_P, _I, _P, _I, _P, _P, _I, _P, _P]),
+    'fva_ema_chunk_elems': (_I, []),
+    'fva_ema_update': (_I, [_P, _I, _P, _I, C.c_double, C.c_double, _P, _P]),
     'fva_paste_resize_normalize': (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
     'fva_paste_resize_u8': (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P]),
     'fva_colour_workspace': (_L, [_I]),
@@ -202,7 +204,7 @@ PROTOTYPES = {
 }
 LABEL_I64, LABEL_F32 = 0, 1
 REDUCE_MEAN, REDUCE_SUM = 0, 1
-UNCHECKED = {'fva_conv_patch_kernel', 'fva_sgd_chunk_elems', 'fva_rows_relu_bwd_rows', 'fva_colour_workspace', 'fva_conv_dgrad_stat_rows', 'fva_bias_relu_bwd_rows', 'fva_colsum_scratch_rows', 'fva_last_error', 'fva_version', 'fva_profile_stop', 'fva_conv_last_kernel', 'fva_conv_packed_elems', 'fva_conv_stat_blocks', 'fva_conv_wgrad_workspace', 'fva_conv_wgrad_plan',
+UNCHECKED = {'fva_conv_patch_kernel', 'fva_sgd_chunk_elems', 'fva_ema_chunk_elems', 'fva_rows_relu_bwd_rows', 'fva_colour_workspace', 'fva_conv_dgrad_stat_rows', 'fva_bias_relu_bwd_rows', 'fva_colsum_scratch_rows', 'fva_last_error', 'fva_version', 'fva_profile_stop', 'fva_conv_last_kernel', 'fva_conv_packed_elems', 'fva_conv_stat_blocks', 'fva_conv_wgrad_workspace', 'fva_conv_wgrad_plan',
              'fva_stem_stat_blocks', 'fva_stem_fused_blocks', 'fva_stem_wgrad_workspace', 'fva_stem_fwd_workspace', 'fva_stem_wgrad_mfma_workspace', 'fva_bn_bwd_blocks', 'fva_bn_partial_rows', 'fva_yolov3_loss_workspace',
              'fva_demo_loss_workspace', 'fva_demo_ciou_loss_workspace', 'fva_nms_candidates_workspace', 'fva_nms_select_workspace', 'fva_softmax_ce_workspace', 'fva_bn_frozen_bwd_blocks'}
 

@@ -82,6 +82,9 @@ class GraphedTrainStep:
     step's side stream is low-priority, which graph kernel nodes cannot be on this runtime) -- so the library's side stream is
     switched off around warm-up and capture and put back afterwards; pass True to capture the two-branch form anyway.
     Several graphs may be captured on one optimizer (another batch size, a re-capture): each owns its pointer-table staging.
+    ``ema`` (ModelEMA, optional): ``ema.update(model)`` follows the optimizer step inside the captured sequence -- its update counter and
+    weight live on the device, so each replay applies the next point of the ramp; warm-up and capture leave the average and its
+    counter untouched, and after each replay the versions of the averaged model's tensors are advanced.
 
         step = GraphedTrainStep(model, lambda pred, tg: criterion(pred, tg), optimizer, images, targets, max_targets=1280)
         for images, targets in loader:
@@ -89,13 +92,13 @@ class GraphedTrainStep:
     """
 
     def __init__(self, model, loss_fn, optimizer, images, targets, max_targets=None, warmup=2, pre_step=None, on_capture=None,
-                 side_stream=False):
+                 side_stream=False, ema=None):
         if not getattr(optimizer, 'capturable', False):
             raise RuntimeError('GraphedTrainStep needs FusedAdam(..., capturable=True) or FusedSGD(..., capturable=True): '
                                'step count and LR must live on the device')
         if not model.training:
             raise RuntimeError('GraphedTrainStep: put the model in train mode first')
-        self.model, self.loss_fn, self.optimizer, self.pre_step = model, loss_fn, optimizer, pre_step
+        self.model, self.loss_fn, self.optimizer, self.pre_step, self.ema = model, loss_fn, optimizer, pre_step, ema
         self.params = [p for g in optimizer.param_groups for p in g['params']]
         T = int(targets.shape[0])
         self.capacity = int(max_targets) if max_targets is not None else T
@@ -142,6 +145,9 @@ class GraphedTrainStep:
             ops.set_wgrad_side_stream(side_was)
         optimizer.set_host_state(host_before)                        # capture ran the host side of optimizer.step() once
         torch.autograd.graph.increment_version(self.params)
+        if ema is not None:
+            ema.bump_versions()
+            self._ema_tables = ema._tab                              # the captured launch reads these device tables: kept alive with the graph
         self.replays = 0
 
     def _step(self):
@@ -152,13 +158,20 @@ class GraphedTrainStep:
         if self.pre_step is not None:
             self.pre_step()
         self.optimizer.step()
+        if self.ema is not None:
+            self.ema.update(self.model)
         return loss.detach()
 
     def _snapshot(self):
-        return snapshot_train_state(self.model, self.optimizer)
+        snap = snapshot_train_state(self.model, self.optimizer)
+        if self.ema is not None:
+            snap['ema'] = self.ema.snapshot_state()
+        return snap
 
     def _restore(self, snap):
         restore_train_state(self.model, self.optimizer, snap)
+        if self.ema is not None:
+            self.ema.restore_state(snap['ema'])
 
     def __call__(self, images=None, targets=None):
         if images is not None:
@@ -178,4 +191,6 @@ class GraphedTrainStep:
         self.replays += 1
         self.optimizer.note_replayed_steps(1)
         torch.autograd.graph.increment_version(self.params)          # eager code that follows must see the parameters as changed
+        if self.ema is not None:
+            self.ema.bump_versions()                                 # ... and the averaged model's tensors
         return self.loss

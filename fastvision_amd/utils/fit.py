@@ -6,6 +6,9 @@ fit.py:73-105: eval-mode forward with decode, validation loss, NMS (conf 0.25, I
 CalculateMAP over IoU 0.5:0.95 -- decode and NMS run in the HIP kernels, one NMS pass per batch instead of one per image, and the
 predictions of a batch are matched to its targets in one launch (CalculateMAP.process_batch): one host read-back per batch (the NMS
 candidate counts), the losses and the mAP rows are read back once at the end.
+
+``ema=`` (fastvision_amd.ModelEMA, not in the reference): updated after every optimizer step; ``_val`` then evaluates the averaged model
+(forward and loss) and the per-epoch checkpoint gains an ``'ema'`` entry.  Without it the loop is the reference's.
 """
 import numpy as np
 import torch
@@ -55,13 +58,14 @@ class stall_watch:
 
 class Fit:
     def __init__(self, model, device, optimizer, scheduler, loss, end_epoch, start_epoch=0, train_loader=None, val_loader=None,
-                 test_loader=None, data_dict=None, log_every=0, save_last='last.pth'):
+                 test_loader=None, data_dict=None, log_every=0, save_last='last.pth', ema=None):
         self.model, self.device, self.optimizer, self.scheduler, self.loss = model, device, optimizer, scheduler, loss
         self.start_epoch, self.end_epoch = start_epoch, end_epoch
         self.train_loader, self.val_loader, self.test_loader = train_loader, val_loader, test_loader
         self.category_names = {k: v for k, v in enumerate((data_dict or {}).get('categories', []))}
         self.log_every = log_every
         self.save_last = save_last                  # None / '' skips the per-epoch checkpoint the reference always writes
+        self.ema = ema                              # ModelEMA: updated after every optimizer step; validation and checkpoints use its average
         self.history = []
 
     def run_epoches(self):
@@ -70,7 +74,10 @@ class Fit:
             if self.val_loader:
                 self._val()
             if self.save_last:                      # fit.py:36-41: the whole model + optimizer state after every epoch
-                SaveModel({'model': self.model, 'optimizer': self.optimizer.state_dict()}, self.save_last, weights_only=True)
+                ckpt = {'model': self.model, 'optimizer': self.optimizer.state_dict()}
+                if self.ema is not None:
+                    ckpt['ema'] = self.ema.state_dict()
+                SaveModel(ckpt, self.save_last, weights_only=True)
         if self.test_loader:
             self._test()
 
@@ -92,6 +99,8 @@ class Fit:
                 loss = self.loss(pred, labels)
                 loss.backward()
                 self.optimizer.step()
+                if self.ema is not None:
+                    self.ema.update(self.model)
             losses.append(loss.detach())          # device tensor: no per-step host sync (the reference's tqdm .item() does one)
             del pred, loss                        # the graph of this step must not outlive it (it would sit in memory beside the next step's)
             if epoch == self.start_epoch and batch_idx == 0:
@@ -108,12 +117,13 @@ class Fit:
         (fit.py:79) this iterates ``train_loader`` when no ``val_loader`` was given."""
         loader = self.val_loader or self.train_loader
         map_est = CalculateMAP(map_iou_values=np.linspace(0.5, 0.95, 10))
-        self.model.eval()
+        model = self.model if self.ema is None else self.ema.module      # with an EMA the averaged model is what is validated
+        model.eval()
         losses, scales = [], {}
         with torch.no_grad():
             for images, labels in loader:
                 images, labels = self._to_device(images, labels)
-                head_out, results = self.model(images, val=True)
+                head_out, results = model(images, val=True)
                 losses.append(self.loss(head_out, labels).detach())       # device tensor, read back once below (as in _train)
                 key = (images.size(3), images.size(2), labels.device, labels.dtype)
                 if key not in scales:                                      # one upload per image size, not one per batch

@@ -572,6 +572,23 @@ int fva_sgd_clip_coef(const int64_t* tab_dev, int32_t n, const int64_t* chunks_d
 int fva_sgd_step(const int64_t* tab_dev, int32_t n, const int64_t* chunks_dev, int32_t nchunks, const float* hyper_dev,
                  int32_t* fresh_dev, int32_t clear_fresh, const float* coef_dev, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Exponential moving average of the weights (fastvision_amd.ModelEMA: the averaged model a YOLO trainer validates and checkpoints),
+ * multi-tensor, counter and weight on the device (a captured training step replays it).  One call = one update:
+ *   a one-thread tick computes, in double, k = state_dev[0] + 1, state_dev[0] = k, d = decay * (1 - exp(-k / tau)) (d = decay when
+ *   tau == 0), state_dev[1] = w = 1 - d;  then one block per chunk applies  e = fmaf((float)w, p - e, e)  to the fp32 tensors (one fp32
+ *   subtraction, one fused multiply-add) and copies the other tensors byte for byte.
+ *   tab_dev: int64 [4][n] in device memory = EMA tensor pointer | model tensor pointer | count | kind; kind 0 = fp32 lerp, count in
+ *            elements, any 4-byte aligned pointers (16-byte vector path where both pointers allow it); kind 1 = raw copy model ->
+ *            EMA, count in bytes, any pointers (integer, bool and non-fp32 float buffers such as num_batches_tracked);
+ *   chunks_dev: int64 [nchunks] = (tensor << 32) | chunk number, a chunk being fva_ema_chunk_elems() fp32 elements (kind 0) or four
+ *            times as many bytes (kind 1);
+ *   state_dev: double [2] = {updates done, weight of the current update}.
+ * decay must lie in [0, 1), tau must be >= 0.  No atomics, no host synchronisation, nothing read back. */
+int fva_ema_chunk_elems(void);
+int fva_ema_update(const int64_t* tab_dev, int32_t n, const int64_t* chunks_dev, int32_t nchunks, double decay, double tau,
+                   double* state_dev, void* stream);
+
 /* Gradient bucket fill for the data-parallel all-reduce (parallel.GradientReducer; the reference's nn.DataParallel gathers
  * gradients tensor by tensor, demos/yolov3_u/train.py:85): dst[offs[t] + i] = src_t[i], converted to dst_dtype (FVA_F32 or
  * FVA_BF16), for n fp32 source tensors in one launch.  table_dev: 3n int64 in device memory = source pointers | element counts |
