@@ -177,6 +177,7 @@ PROTOTYPES = {
     'fva_maxpool2_fwd': (_I, [_I, _P, _I, _P, _I, _I, _I, _I, _I, _P]),
     'fva_maxpool2_bwd': (_I, [_I, _P, _P, _I, _P, _I, _I, _I, _I, _P]),
     'fva_rpn_decode': (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    'fva_fast_decode': (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _F, _F, _F, _P, _P, _P]),
     'fva_rpn_match': (_I, [_P, _I, _P, _I, _I, _I, _I, _F, _F, _P, _P, _P]),
     'fva_fast_match': (_I, [_P, _I, _P, _I, _I, _F, _F, _F, _P, _P]),
     'fva_roi_align_fwd': (_I, [_I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _F, _I, _P]),

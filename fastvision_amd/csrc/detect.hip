@@ -460,6 +460,108 @@ extern "C" int fva_rpn_decode(const float* cls, const float* deltas, const float
     return FVA_OK;
 }
 
+// ---- second-stage head outputs -> NMS rows (demos/faster_rcnn/models/fast.py:93-101,265-286 + inference.py:87-118) -----------------
+// One wave per (image, row) of the PADDED output pred [B][R][5 + C]: the wave reads its source row's C + 1 logits (coalesced, lane
+// = column), reduces them three times (first maximum logit; sum of exp; first maximum probability -- torch.max's rule, as in
+// cand_score_kernel), every lane then decodes the box (uniform loads) and the lanes write the output row, column = lane.  Rows at or
+// past an image's count, and rows the reference drops (background, w or h <= min_wh), are written as (0, 0, 0, 0, -1, 0, ...): the
+// -1 is below any confidence threshold.  Output-driven: nothing is scattered and pred's earlier contents are never read.
+// Quirk kept: BOTH extents use exp(d[2]) (fast.py:98-99).  expf, not __expf; this file is built with -ffp-contract=off.
+namespace {
+__global__ __launch_bounds__(256) void fast_decode_kernel(const float* __restrict__ cls, const float* __restrict__ box,
+                                                          const float* __restrict__ prop, const int32_t* __restrict__ row_start, int K,
+                                                          int B, int R, int C, int multi_reg, float stride, float in_w, float in_h,
+                                                          float min_wh, const fva_letterbox* __restrict__ lb, float* __restrict__ pred) {
+    const int lane = threadIdx.x & 63;
+    const int64_t item = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);        // wave-uniform
+    if (item >= (int64_t)B * R) return;
+    const int b = (int)(item / R), r = (int)(item - (int64_t)b * R);
+    const int C1 = C + 1, cols = 5 + C;
+    float* o = pred + item * cols;
+    const int first = row_start[b], n = row_start[b + 1] - first;
+    const int64_t src = (int64_t)first + r;
+    float x1 = 0.f, y1 = 0.f, x2 = 0.f, y2 = 0.f, score = -1.f;
+    int cat = 0;                                                              // 0 = dropped
+    if (r < n && first >= 0 && src < K) {                                      // a row_start that points outside the K rows reads nothing
+        const float* z = cls + src * C1;
+        float best = -INFINITY;
+        int m = 0x7fffffff;
+        for (int c = lane; c < C1; c += 64) {
+            const float v = z[c];
+            if (v > best) { best = v; m = c; }
+        }
+#pragma unroll
+        for (int s = 32; s > 0; s >>= 1) {
+            const float ov = __shfl_xor(best, s);
+            const int oi = __shfl_xor(m, s);
+            if (ov > best || (ov == best && oi < m)) { best = ov; m = oi; }
+        }
+        float sum = 0.f;
+        for (int c = lane; c < C1; c += 64) sum += expf(z[c] - best);
+#pragma unroll
+        for (int s = 32; s > 0; s >>= 1) sum += __shfl_xor(sum, s);             // a + b == b + a: every lane ends with the same bits
+        float pbest = -INFINITY;
+        int pc = 0x7fffffff;
+        for (int c = lane; c < C1; c += 64) {
+            const float p = expf(z[c] - best) / sum;
+            if (p > pbest) { pbest = p; pc = c; }
+        }
+#pragma unroll
+        for (int s = 32; s > 0; s >>= 1) {
+            const float ov = __shfl_xor(pbest, s);
+            const int oi = __shfl_xor(pc, s);
+            if (ov > pbest || (ov == pbest && oi < pc)) { pbest = ov; pc = oi; }
+        }
+        if (m != 0x7fffffff && pc != 0x7fffffff && pc > 0) {                   // all-NaN logits, or background: dropped
+            const float* d = box + src * (multi_reg ? (int64_t)C1 * 4 : 4) + (multi_reg ? m * 4 : 0);
+            const float* q = prop + src * 4;
+            const float4 pr = make_float4(q[0], q[1], q[2], q[3]);
+            const float d0 = d[0] * 0.1f, d1 = d[1] * 0.1f, d2 = d[2] * 0.2f;
+            const float e = expf(d2);
+            float x = (d0 * pr.z + pr.x) * stride, y = (d1 * pr.w + pr.y) * stride;
+            float w = e * pr.z * stride, h = e * pr.w * stride;
+            float ratio = 1.f, pl = 0.f, pt = 0.f, bw = in_w, bh = in_h;
+            if (lb) { ratio = lb[b].resize_ratio; pl = lb[b].pad_left; pt = lb[b].pad_top; bw = lb[b].ori_w; bh = lb[b].ori_h; }
+            x = clampf((x - pl) / ratio, 0.f, bw - 1.f);
+            y = clampf((y - pt) / ratio, 0.f, bh - 1.f);
+            w = clampf(w / ratio, 0.f, bw);
+            h = clampf(h / ratio, 0.f, bh);
+            if (w > min_wh && h > min_wh) {
+                x1 = clampf(x - w / 2.f, 0.f, bw - 1.f);
+                y1 = clampf(y - h / 2.f, 0.f, bh - 1.f);
+                x2 = clampf(x + w / 2.f, 0.f, bw - 1.f);
+                y2 = clampf(y + h / 2.f, 0.f, bh - 1.f);
+                score = pbest;
+                cat = pc;
+            }
+        }
+    }
+    for (int c = lane; c < cols; c += 64) {
+        float v = 0.f;
+        if (c == 4) v = score;
+        else if (cat > 0) v = c == 0 ? x1 : c == 1 ? y1 : c == 2 ? x2 : c == 3 ? y2 : (c - 5 == cat - 1 ? 1.f : 0.f);
+        o[c] = v;
+    }
+}
+}  // namespace
+
+extern "C" int fva_fast_decode(const float* cls, const float* box, const float* proposals, const int32_t* row_start, int32_t K, int32_t B,
+                               int32_t R, int32_t C, int32_t multi_reg, float stride, float in_w, float in_h, float min_wh,
+                               const fva_letterbox* lb, float* pred, void* stream) {
+    if (!row_start || !pred) return fva_fail(FVA_ERR_ARG, "fva_fast_decode: null pointer");
+    if (K < 0 || (K > 0 && (!cls || !box || !proposals))) return fva_fail(FVA_ERR_ARG, "fva_fast_decode: K=%d rows without their arrays", K);
+    if (B < 1 || R < 1 || C < 1) return fva_fail(FVA_ERR_ARG, "fva_fast_decode: bad shape B=%d R=%d C=%d", B, R, C);
+    if ((multi_reg | 1) != 1) return fva_fail(FVA_ERR_ARG, "fva_fast_decode: multi_reg must be 0 or 1");
+    if (!(stride > 0.f) || !(in_w >= 1.f) || !(in_h >= 1.f) || !(min_wh >= 0.f))
+        return fva_fail(FVA_ERR_ARG, "fva_fast_decode: stride, in_w, in_h must be positive and min_wh >= 0");
+    const int64_t items = (int64_t)B * R;
+    if (items * (5 + (int64_t)C) >= (1ll << 31) || (int64_t)K * (C + 1) * 4 >= (1ll << 31)) return fva_fail(FVA_ERR_ARG, "fva_fast_decode: too large");
+    hipLaunchKernelGGL(fast_decode_kernel, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, (hipStream_t)stream, cls, box, proposals, row_start,
+                       K, B, R, C, multi_reg, stride, in_w, in_h, min_wh, lb, pred);
+    FVA_LAUNCH_CHECK("fast_decode_kernel");
+    return FVA_OK;
+}
+
 // ---- RPN anchor / ground-truth matcher (demos/faster_rcnn/models/rpn.py:209-277) ------------------------------
 // Per image: IoU of every anchor (xywh, feature cells) with every ground-truth box of that image (normalised xywh scaled by the
 // map size), then the reference's labelling: label = index of the best box if its IoU > pos_thr, -1 (negative) if the best IoU <

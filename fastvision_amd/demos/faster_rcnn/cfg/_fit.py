@@ -7,6 +7,10 @@ reference leaves its .cuda() calls commented out and relies on DataParallel), th
 read-back instead of one per parameter, and the per-batch print reads the five loss values back in one transfer.  An optimizer
 that clips by itself (``clip_norm`` set, e.g. fastvision_amd.FusedSGD(..., clip_norm=10.): norm and coefficient on the device, no
 read-back) replaces the clip_gradient call.
+
+``Validate`` (the reference's Fit takes a validation_loader and never uses it): mAP over a loader with the batched device path --
+Faster_Rcnn.detect and CalculateMAP.process_batch; ``Fit`` calls it after each epoch when a validation_loader is given, prints
+mAP@0.5 and mAP@0.5:0.95 and goes back to train(); without a loader the loop is the reference's.
 """
 import torch
 
@@ -42,6 +46,40 @@ def _Train(model, train_loader, optimizer, log=print):
             log(*torch.cat([loss.detach().reshape(1), parts.detach()]).tolist())
 
 
+def targets_to_pixels(targets, height, width):
+    """[T, 6] = image, class, normalised xywh (the training format) -> [T, 6] = image, class, xyxy in input pixels (what
+    CalculateMAP.process_batch matches the detections against)."""
+    from ..utils import xywh2xyxy
+    scale = torch.tensor([width, height, width, height]).to(targets)
+    return torch.cat([targets[:, :2], xywh2xyxy(targets[:, 2:6]) * scale], dim=1)
+
+
+@torch.no_grad()
+def Validate(model, validation_loader, args, metric=None):
+    """mAP of a Faster R-CNN model over ``validation_loader`` (batches of images [B,3,H,W] and targets [T,6] = image, class, normalised
+    xywh), entirely on the device: per batch one ``detect`` (input-pixel frame, thresholds args.inference_conf_thres /
+    inference_iou_thres) and one matching launch (``metric.process_batch``); the rows are read back once, by ``metric.fetch()``, whose
+    value -- (mAP per IoU threshold, mAP per class, class ids) -- is returned (zeros and no classes when nothing was detected or no
+    target was seen).  The model is evaluated in eval() mode and put back into the mode it came in."""
+    import numpy as np
+    from ....metrics import CalculateMAP
+    metric = CalculateMAP(np.linspace(0.5, 0.95, 10)) if metric is None else metric
+    net = model.module if hasattr(model, 'module') else model
+    was_training = net.training
+    net.eval()
+    try:
+        for images, targets in validation_loader:
+            images, targets = images.cuda(non_blocking=True), targets.cuda(non_blocking=True)
+            dets, kept = net.detect(images, args.inference_conf_thres, args.inference_iou_thres)
+            metric.process_batch(dets, kept, targets_to_pixels(targets.float(), images.size(2), images.size(3)))
+    finally:
+        net.train(was_training)
+    metric.materialize()
+    if not (metric.correct_all_images and metric.seen_all_targets_cls):
+        return np.zeros(len(metric.map_iou_values)), np.zeros(0), []
+    return metric.fetch()
+
+
 def Fit(model, args, optimizer, train_loader, validation_loader=None):
     for epoch in range(args.start_epoch, args.total_epoch):
         if (epoch + 1) % 9 == 0:
@@ -51,3 +89,7 @@ def Fit(model, args, optimizer, train_loader, validation_loader=None):
         _Train(model, train_loader, optimizer)
         state = (model.module if hasattr(model, 'module') else model).state_dict()
         torch.save(state, f'./{epoch + 1}.pth')
+        if validation_loader is not None:
+            map_each_iou = Validate(model, validation_loader, args)[0]
+            print('Epoch {} mAP@0.5 : {:.4f}  mAP@0.5:0.95 : {:.4f}'.format(epoch + 1, float(map_each_iou[0]), float(map_each_iou.mean())))
+            model.train()

@@ -1,7 +1,8 @@
 """API mirror of the reference's demos/faster_rcnn/inference.py on the device ops: ``preProcess`` (ResizeByMax + Padding(128) + / 255
 in one kernel launch), ``postProcess`` (feature cells -> input pixels -> original image, clamps, the 5-pixel filter, per-class NMS),
 ``anchor_fn``, ``model_fn`` and the ``Inference`` loop (detections are returned / printed; the reference's cv2.imshow viewer is not
-part of this package)."""
+part of this package).  ``Inference(..., batch_size=N)`` with N > 1 takes the files in groups through ``Faster_Rcnn.detect`` (one
+preprocessing launch, one heads pass, one decode launch and one NMS per group) and returns the same dict."""
 import os
 from glob import glob
 
@@ -65,13 +66,40 @@ def model_fn(args, base_anchors):
     return model.to(getattr(args, 'device', 'cuda'))
 
 
+def _detect_group(model, args, files, device):
+    """``batch_size`` files at once: one val_batch launch, one model.detect with the per-image letterboxes (the arithmetic of preProcess),
+    one read-back of the kept counts for the slicing -> per file (scores [m,1], categories [m,1], boxes [m,4]) as postProcess returns."""
+    from ...datasets.detection_dataloader import _decode_rgb
+    S = args.input_size
+    originals = [_decode_rgb(f) for f in files]
+    letterboxes = []
+    for img in originals:
+        ori_height, ori_width = img.shape[:2]
+        resize_ratio = S / max(ori_height, ori_width)
+        resize_width, resize_height = int(ori_width * resize_ratio), int(ori_height * resize_ratio)
+        letterboxes.append((resize_ratio, (S - resize_width) // 2, (S - resize_height) // 2, ori_width, ori_height))
+    empty = (np.zeros((0, 4), np.float32), np.zeros((0,), np.float32))
+    images, _ = DeviceAugmenter(S, device).val_batch([(img,) + empty for img in originals])
+    dets, kept = model.detect(images, args.inference_conf_thres, args.inference_iou_thres, max_det=300, letterboxes=letterboxes)
+    kept = kept.cpu().tolist()
+    return [(dets[b, :n, 4:5], dets[b, :n, 5:6], dets[b, :n, 0:4]) for b, n in enumerate(kept)]
+
+
 @torch.no_grad()
-def Inference(args, image_dir, log=print):
-    """The reference's loop (inference.py:158-224) over ``image_dir``/*.jpg|png: returns {file: (scores, categories, boxes)}."""
+def Inference(args, image_dir, log=print, batch_size=1):
+    """The reference's loop (inference.py:158-224) over ``image_dir``/*.jpg|png: returns {file: (scores, categories, boxes)}.
+    ``batch_size`` > 1 (not in the reference): the files are taken in groups, each group one batched ``Faster_Rcnn.detect``."""
     base_anchors = anchor_fn(args.scales, args.ratios)
     model = model_fn(args=args, base_anchors=base_anchors)
     out = {}
     files = sorted(glob(os.path.join(image_dir, '*.jpg')) + glob(os.path.join(image_dir, '*.png')))
+    if batch_size > 1:
+        for i in range(0, len(files), batch_size):
+            group = files[i:i + batch_size]
+            for file, result in zip(group, _detect_group(model, args, group, getattr(args, 'device', 'cuda'))):
+                out[file] = result
+                log(f'{os.path.basename(file)}: {result[2].size(0)} detections')
+        return out
     for file in files:
         image, ori_img, resize_ratio, padding_left, padding_top, ori_height, ori_width = preProcess(file, args.input_size, getattr(args, 'device', 'cuda'))
         predicts = model(image)

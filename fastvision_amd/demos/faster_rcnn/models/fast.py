@@ -6,6 +6,8 @@ same constructor arguments, parameter names and return values).
                class logits and box regression -> cross-entropy over positives + negatives, smooth-L1 on the positives'
                regression against targets normalised by std (0.1, 0.1, 0.2, 0.2)
     inference: per image RoIAlign of its proposals, heads, decode, arg-max class, background dropped -> [n, 6] = xywh, class, score
+    detect:    the same for the whole batch at once -- one heads pass over every image's RoIs, one fva_fast_decode launch that also does
+               postProcess's frame change, clamps and size filter -> padded NMS rows [B, R, 5 + classes] (not in the reference)
 
 The fully connected layers (25088 -> 4096 -> 4096 -> classes / boxes) run on the library's implicit-GEMM kernels as 1x1 convolutions
 over the RoI rows (fc_ops.linear_relu: bias + ReLU epilogue; fc_ops.linear: the biased head convolution), cross-entropy and smooth-L1
@@ -18,7 +20,7 @@ import torch.nn.functional as F
 
 from ....fc_ops import cross_entropy_mean, linear, linear_relu, smooth_l1_mean
 from ....roi_ops import roi_align
-from ....rpn_ops import fast_select_samples
+from ....rpn_ops import fast_decode, fast_select_samples
 
 __all__ = ['Fast']
 
@@ -76,6 +78,28 @@ class Fast(nn.Module):
         logits = torch.cat([positive_cls, negative_cls], dim=0)
         labels = torch.cat([target_cls.view(-1) + 1, torch.zeros(negative_cls.size(0)).to(target_cls)], dim=0).long()
         return cross_entropy_mean(logits, labels), loss_box
+
+    def _detect_heads(self, feature_backbone, proposals):
+        """The RoIs of ALL images (image index = list position) through ONE _heads call: the 205 MB of classifier weights stream once
+        per batch.  -> (cls [K, C+1], box, xywh [K, 4], row_start [B+1] int32 on the device, R); the counts are host-known shapes."""
+        device = feature_backbone.device
+        counts = [int(p.size(0)) for p in proposals]
+        starts = [0]
+        for n in counts:
+            starts.append(starts[-1] + n)
+        row_start = torch.tensor(starts, dtype=torch.int32).to(device)
+        xywh = torch.cat([p.float() for p in proposals], 0) if counts else torch.zeros((0, 4), device=device)
+        index = torch.cat([torch.full((n, 1), float(b), device=device) for b, n in enumerate(counts)], 0) if counts else xywh[:, :1]
+        cls, box = self._heads(feature_backbone, torch.cat([index, _xyxy(xywh)], 1))
+        return cls, box, xywh, row_start, max(max(counts, default=0), 1)
+
+    def detect(self, feature_backbone, proposals, stride, input_hw, letterboxes=None, min_wh=5.0):
+        """The eval branch of forward and inference.postProcess up to its NMS call for the whole batch: one heads pass, one decode launch
+        (rpn_ops.fast_decode), no host read-back.  proposals: list over images of [n, 4] xywh in feature cells (the RPN's output; an image
+        may have none) -> pred [B, max(n_b, 1), 5 + classes] for detect_ops.nms_batch_padded(..., NMS_DEMO): xyxy in input pixels, or in
+        each image's original frame when ``letterboxes`` (per image resize_ratio, pad_left, pad_top, ori_w, ori_h) is given."""
+        cls, box, xywh, row_start, R = self._detect_heads(feature_backbone, proposals)
+        return fast_decode(cls, box, xywh, row_start, R, stride, input_hw, letterboxes, min_wh, self.fast_multi_reg_head)
 
     def forward(self, feature_backbone, proposals, targets=None, perms=None):
         bs, c, h, w = feature_backbone.shape

@@ -11,7 +11,7 @@ from . import _lib
 from .detect_ops import nms_batch
 from .ops import _p, _stream, require_gpu
 
-__all__ = ['filter_proposals', 'rpn_proposal_rows', 'rpn_match', 'rpn_sample', 'fast_match', 'fast_select_samples']
+__all__ = ['filter_proposals', 'rpn_proposal_rows', 'rpn_match', 'rpn_sample', 'fast_match', 'fast_select_samples', 'fast_decode']
 
 _MODE = dict(box_mode=1, score_mode=1, rethreshold=0, class_gap=0.0)
 
@@ -92,6 +92,47 @@ def fast_match(proposals_xywh, targets, image, pos_thr=0.5, neg_thr=0.5, neg_flo
     _lib.call('fva_fast_match', _p(prop) if N else None, N, _p(tg) if T else None, T, int(image), float(pos_thr), float(neg_thr),
               float(neg_floor), _p(labels) if N else None, _stream())
     return labels.long()
+
+
+def fast_decode(cls, box, proposals, row_start, R, stride, input_hw, letterboxes=None, min_wh=5.0, multi_reg=False):
+    """Second-stage head outputs of a whole batch -> the NMS input rows, in one launch and without a host read-back (`fva_fast_decode`:
+    fast.py:93-101,265-286 + inference.py:87-118 up to the NMS call).  cls [K, C+1] logits (column 0 = background), box [K, 4] (or
+    [K, (C+1)*4] with ``multi_reg``), proposals [K, 4] xywh in feature cells, image after image; row_start [B+1] int32 on the device (image
+    b owns rows row_start[b] .. row_start[b+1]-1, at most ``R``).  input_hw = (height, width) of the network input: the frame of the rows
+    when ``letterboxes`` is None; otherwise one (resize_ratio, pad_left, pad_top, ori_w, ori_h) per image maps them to its original image.
+    -> pred [B, R, 5+C] = clamped xyxy, score, one-hot category; dropped rows (padding, background, w or h <= min_wh) carry score -1:
+    what ``detect_ops.nms_batch_padded(pred, ..., NMS_DEMO)`` takes."""
+    require_gpu(cls, 'fast_decode')
+    require_gpu(row_start, 'fast_decode (row_start)')
+    if cls.dim() != 2 or cls.size(1) < 2:
+        raise ValueError(f'fast_decode: cls must be [K, C+1] with C >= 1, got {tuple(cls.shape)}')
+    K, C = cls.size(0), cls.size(1) - 1
+    want_box = (C + 1) * 4 if multi_reg else 4
+    if tuple(box.shape) != (K, want_box):
+        raise ValueError(f'fast_decode: box must be [{K}, {want_box}], got {tuple(box.shape)}')
+    if tuple(proposals.shape) != (K, 4):
+        raise ValueError(f'fast_decode: proposals must be [{K}, 4], got {tuple(proposals.shape)}')
+    if row_start.dim() != 1 or row_start.numel() < 2 or row_start.dtype != torch.int32:
+        raise ValueError('fast_decode: row_start must be an int32 vector of B + 1 entries')
+    B, R = row_start.numel() - 1, int(R)
+    if R < 1:
+        raise ValueError(f'fast_decode: R must be >= 1, got {R}')
+    dev = cls.device
+    cls, box = cls.detach().float().contiguous(), box.detach().float().contiguous()
+    proposals, row_start = proposals.detach().float().contiguous(), row_start.contiguous()
+    lb = None
+    if letterboxes is not None:
+        if len(letterboxes) != B:
+            raise ValueError(f'fast_decode: {len(letterboxes)} letterboxes for {B} images')
+        rows = [[float(v) for v in one[:5]] + [float(min_wh)] for one in letterboxes]
+        if any(len(r) != 6 or not r[0] > 0 for r in rows):
+            raise ValueError('fast_decode: a letterbox is (resize_ratio > 0, pad_left, pad_top, ori_w, ori_h)')
+        lb = torch.tensor(rows, dtype=torch.float32).to(dev)              # [B] fva_letterbox, an upload: nothing is read back
+    pred = torch.empty((B, R, 5 + C), dtype=torch.float32, device=dev)
+    _lib.call('fva_fast_decode', _p(cls) if K else None, _p(box) if K else None, _p(proposals) if K else None, _p(row_start), K, B, R, C,
+              1 if multi_reg else 0, float(stride), float(input_hw[1]), float(input_hw[0]), float(min_wh), _p(lb) if lb is not None else None,
+              _p(pred), _stream())
+    return pred
 
 
 def fast_select_samples(proposals, targets, pos_thr=0.5, neg_thr=0.5, positives_per_image=16, negatives_per_image=48, perms=None):

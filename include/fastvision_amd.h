@@ -630,6 +630,24 @@ int fva_maxpool2_bwd(int dtype, const void* dz, const void* x, int x_pad, void* 
 int fva_rpn_decode(const float* cls, const float* deltas, const float* anchors_wh, float* out, int32_t B, int32_t H, int32_t W,
                    int32_t A, void* stream);
 
+/* Second-stage head outputs of a whole batch -> the rows fva_nms_candidates takes (box_mode 1, score_mode 1), in ONE launch:
+ * Fast.forward's eval branch and postProcess up to the NMS call (demos/faster_rcnn/models/fast.py:93-101,265-286,
+ * demos/faster_rcnn/inference.py:87-118).  cls [K][C+1] logits (column 0 = background); box [K][4], or [K][(C+1)*4] with
+ * multi_reg = 1 (the four of the row's first-maximum LOGIT are used); proposals [K][4] xywh in feature cells, image after image;
+ * row_start [B+1] i32 on the device: image b owns rows row_start[b] .. row_start[b+1]-1, at most R of them (the caller's promise;
+ * rows past R are not decoded, and a range that leaves [0, K) reads nothing).  pred [B][R][5+C] fp32, every element written:
+ *   d = box * (0.1, 0.1, 0.2, 0.2); x = d0*pw + px, y = d1*ph + py, w = exp(d2)*pw, h = exp(d2)*ph (d2 twice, as the reference);
+ *   score / category = value / first index of the maximum softmax probability; xywh * stride; then with lb == NULL the clamps
+ *   of postProcess with ratio 1, pads 0 and bounds in_w / in_h (the input-pixel frame), with lb [B] (device) image b's
+ *   (x - pad_left) / resize_ratio etc. against ori_w / ori_h (lb[b].min_wh is not read: min_wh is the argument);
+ *   row = clamped x1, y1, x2, y2, score, then 1.0 in column 5 + category - 1 and 0 elsewhere.
+ * A row is DROPPED -- written as 0, 0, 0, 0, -1, 0, ... so that no threshold passes it -- when it lies at or past its image's
+ * count, when its category is background (a tie with background included), or when !(w > min_wh && h > min_wh).
+ * K = 0 is allowed (cls, box, proposals may be NULL): every row is dropped. */
+int fva_fast_decode(const float* cls, const float* box, const float* proposals, const int32_t* row_start, int32_t K, int32_t B,
+                    int32_t R, int32_t C, int32_t multi_reg, float stride, float in_w, float in_h, float min_wh,
+                    const fva_letterbox* lb, float* pred, void* stream);
+
 /* RPN anchor / ground-truth matcher: the labelling inside RPN.computet_loss (demos/faster_rcnn/models/rpn.py:209-277).
  * anchors_xywh [Na][4] in feature cells (make_anchors_xywh, flattened (y, x, a)); targets [T][6] = image index, class, normalised
  * xywh (scaled by the map size here, rpn.py:257).  labels [B][Na] i32: >= 0 index of the matched box WITHIN its image's boxes,
