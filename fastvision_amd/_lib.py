@@ -31,6 +31,32 @@ class HeadLevel(C.Structure):
                 ('anchor_w', C.c_float * 8), ('anchor_h', C.c_float * 8), ('stride', C.c_float)]
 
 
+def head_level(data, grad, shape, strides, anchors=(), stride=1.0):
+    """fva_head_level of a head addressed as [B, A, H, W, K] = ``shape`` through the element strides (sb, sa, sy, sx, sk).  data, grad:
+    addresses; grad (None = no gradient) is a buffer with the same strides.  anchors: up to eight (w, h); the other slots stay zero."""
+    lv = HeadLevel()
+    lv.data, lv.grad = data, grad
+    lv.sb, lv.sa, lv.sy, lv.sx, lv.sk = strides
+    lv.B, lv.A, lv.H, lv.W, lv.K = shape
+    for i, (w, h) in enumerate(anchors):
+        lv.anchor_w[i], lv.anchor_h[i] = float(w), float(h)
+    lv.stride = float(stride)
+    return lv
+
+
+def head_level_5d(h, grad, anchors=(), stride=1.0):
+    """head_level of a tensor [B, A, H, W, K] of any strides and its gradient buffer (a tensor with the same strides, or None)."""
+    return head_level(h.data_ptr(), None if grad is None else grad.data_ptr(), h.shape, h.stride(), anchors, stride)
+
+
+def head_level_nchw(h, grad, A, anchors=(), stride=1.0):
+    """head_level of a tensor [B, A * K, H, W] of any strides whose channel is c = a * K + k (the demos' heads), and its gradient buffer."""
+    B, ch, H, W = h.shape
+    K = ch // A
+    sb, sc, sy, sx = h.stride()
+    return head_level(h.data_ptr(), None if grad is None else grad.data_ptr(), (B, A, H, W, K), (sb, K * sc, sy, sx, sc), anchors, stride)
+
+
 class PackEntry(C.Structure):
     _fields_ = [('w', C.c_void_p), ('w_fwd', C.c_void_p), ('w_dgrad', C.c_void_p)] + \
                [(n, C.c_int32) for n in ('Cout', 'Cin', 'ksize', 'taps_fwd', 'taps_dgrad', 'dtype', 'dgrad_paired', 'tile_start')]

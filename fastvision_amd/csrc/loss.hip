@@ -140,6 +140,16 @@ __device__ __forceinline__ D4 ciou_d(const BoxD& a, const BoxD& b, float eps, in
 
 __device__ __forceinline__ float sigm(float x) { return 1.f / (1.f + expf(-x)); }
 
+// sum of v over a 256-thread block, written to *out by thread 0: wave shuffles, one LDS slot per wave, and the fixed association
+// (w0 + w1) + (w2 + w3) of the losses' block partials.  v (left holding its wave's sum) and the slots are the kernel's own: with a
+// by-value v or slots declared here the kernels no longer compile to the instructions they had with this block written out.
+__device__ __forceinline__ void block_sum_store(float& v, float (&wsum)[4], float* out) {
+    v = wave_sum(v);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) *out = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+}
+
 // ---------------------------------------------------------------------------------------------------------
 struct Level {  // device copy of fva_head_level
     float* data;
@@ -321,10 +331,7 @@ __global__ __launch_bounds__(256) void conf_kernel(const Level lv, const int32_t
         acc += -t * logf(p + BCE_EPS) - (1.f - t) * logf(1.f - p + BCE_EPS);
         if (lv.grad) lv.grad[off] = g * (-t / (p + BCE_EPS) + (1.f - t) / (1.f - p + BCE_EPS)) * p * (1.f - p);
     }
-    acc = wave_sum(acc);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) partial[blockIdx.x] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+    block_sum_store(acc, wsum, partial + blockIdx.x);
 }
 
 struct FinalArgs {
@@ -406,7 +413,15 @@ __global__ void demo_group_kernel(const float* __restrict__ tg, int T, int B, in
 
 __device__ __forceinline__ float bce_logits(float z, float t) { return fmaxf(z, 0.f) - z * t + log1pf(expf(-fabsf(z))); }
 
-// one wavefront per target: best anchor, cell, xy / wh / class terms and their gradients (lossv3.py:44-84)
+// The two demo losses are one pipeline with two box terms:
+//   BOX_XYWH (demos/yolov3_u/utils/lossv3.py:44-84): BCE(xy) in db.l_xy and MSE(wh) in db.l_wh, total = 2 xy + wh + cls + conf;
+//   BOX_CIOU (demos/yolov3_huaweiShip/utils/lossv3.py:35-95): 1 - CIoU(pred, target; 'xywh') of the demo's CIoU (centre sums not halved,
+//   minus sign) in db.l_xy, with pred = (sigmoid(z_xy) + cell, exp(z_wh) * anchor); db.l_wh is not used; total = box + cls + conf.
+enum DemoBox { BOX_XYWH = 0, BOX_CIOU = 1 };
+
+// one wavefront per target: best anchor, cell, the class term across the lanes and the box term on lane 0, with their gradients.
+// d (1 - CIoU) / d (x, y, w, h) comes from the forward-mode duals, followed by dx/dz = s (1 - s) and dw/dz = w.
+template <int BOX>
 __global__ __launch_bounds__(256) void demo_target_kernel(const float* __restrict__ tg, int T, const Level lv, const DemoBuf db) {
     const int lane = threadIdx.x & 63, wpb = blockDim.x >> 6;
     const int C = lv.K - 5;
@@ -424,7 +439,7 @@ __global__ __launch_bounds__(256) void demo_target_kernel(const float* __restric
         const int b = (int)tg[t * 6], gx = (int)gxf, gy = (int)gyf, cls = (int)tg[t * 6 + 1];
         const bool ok = b >= 0 && b < lv.B && gx >= 0 && gx < lv.W && gy >= 0 && gy < lv.H;  // reference: IndexError otherwise
         if (!ok) {
-            if (lane == 0) { db.l_xy[t] = 0.f; db.l_wh[t] = 0.f; db.l_cls[t] = 0.f; db.cell[t] = -1; }
+            if (lane == 0) { db.l_xy[t] = 0.f; if constexpr (BOX == BOX_XYWH) db.l_wh[t] = 0.f; db.l_cls[t] = 0.f; db.cell[t] = -1; }
             continue;
         }
         const int64_t base = b * lv.sb + best * lv.sa + gy * lv.sy + gx * lv.sx;
@@ -439,92 +454,68 @@ __global__ __launch_bounds__(256) void demo_target_kernel(const float* __restric
         lsum = wave_sum(lsum);
         if (lane == 0) {
             const float z0 = lv.data[base], z1 = lv.data[base + lv.sk], z2 = lv.data[base + 2 * lv.sk], z3 = lv.data[base + 3 * lv.sk];
-            const float ox = tx - gxf, oy = ty - gyf;
-            const float twh0 = logf(tw / lv.aw[best] + 1e-14f), twh1 = logf(th / lv.ah[best] + 1e-14f);
-            db.l_xy[t] = bce_logits(z0, ox) + bce_logits(z1, oy);
-            db.l_wh[t] = (z2 - twh0) * (z2 - twh0) + (z3 - twh1) * (z3 - twh1);
-            db.l_cls[t] = lsum;
-            db.cell[t] = ((b * lv.H + gy) * lv.W + gx) * lv.A + best;
-            if (lv.grad) {
-                const float g2 = 1.f / (2.f * (float)T);
-                atomicAdd(&lv.grad[base], 2.f * (sigm(z0) - ox) * g2);  // loss_xy carries weight 2.0 (:111)
-                atomicAdd(&lv.grad[base + lv.sk], 2.f * (sigm(z1) - oy) * g2);
-                atomicAdd(&lv.grad[base + 2 * lv.sk], 2.f * (z2 - twh0) * g2);
-                atomicAdd(&lv.grad[base + 3 * lv.sk], 2.f * (z3 - twh1) * g2);
+            // each branch keeps its own stores and atomics, in its own order: sharing them changes the instruction schedule
+            if constexpr (BOX == BOX_XYWH) {
+                const float ox = tx - gxf, oy = ty - gyf;
+                const float twh0 = logf(tw / lv.aw[best] + 1e-14f), twh1 = logf(th / lv.ah[best] + 1e-14f);
+                db.l_xy[t] = bce_logits(z0, ox) + bce_logits(z1, oy);
+                db.l_wh[t] = (z2 - twh0) * (z2 - twh0) + (z3 - twh1) * (z3 - twh1);
+                db.l_cls[t] = lsum;
+                db.cell[t] = ((b * lv.H + gy) * lv.W + gx) * lv.A + best;
+                if (lv.grad) {
+                    const float g2 = 1.f / (2.f * (float)T);
+                    atomicAdd(&lv.grad[base], 2.f * (sigm(z0) - ox) * g2);  // loss_xy carries weight 2.0 (:111)
+                    atomicAdd(&lv.grad[base + lv.sk], 2.f * (sigm(z1) - oy) * g2);
+                    atomicAdd(&lv.grad[base + 2 * lv.sk], 2.f * (z2 - twh0) * g2);
+                    atomicAdd(&lv.grad[base + 3 * lv.sk], 2.f * (z3 - twh1) * g2);
+                }
+            } else {
+                const float sx = sigm(z0), sy = sigm(z1);
+                const float px = sx + gxf, py = sy + gyf;  // :65-69
+                const float pw = expf(z2) * lv.aw[best], ph = expf(z3) * lv.ah[best];
+                const BoxD pb = xywh2xyxy_d(dvar(px, 0), dvar(py, 1), dvar(pw, 2), dvar(ph, 3));
+                const BoxD tb = xywh2xyxy_d(dconst(tx), dconst(ty), dconst(tw), dconst(th));
+                const D4 ciou = ciou_d(pb, tb, IOU_EPS, 1, nullptr);  // :87
+                db.l_xy[t] = 1.f - ciou.v;
+                db.l_cls[t] = lsum;
+                db.cell[t] = ((b * lv.H + gy) * lv.W + gx) * lv.A + best;
+                if (lv.grad) {
+                    const float gb = 1.f / (float)T;  // :88 mean over the targets
+                    const float dpdz[4] = {sx * (1.f - sx), sy * (1.f - sy), pw, ph};
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) atomicAdd(&lv.grad[base + i * lv.sk], -(ciou.d[i] * dpdz[i]) * gb);
+                }
             }
         }
     }
 }
 
-// the ship demo's form of the same kernel (demos/yolov3_huaweiShip/utils/lossv3.py:35-95): best anchor and cell as above, the class term
-// across the lanes, and on lane 0 the box term 1 - CIoU(pred, target; 'xywh') of the demo's CIoU (centre sums not halved, minus sign), with
-// pred = (sigmoid(z_xy) + cell, exp(z_wh) * anchor).  d (1 - CIoU) / d (x, y, w, h) comes from the forward-mode duals, followed by
-// dx/dz = s (1 - s) and dw/dz = w.  db.l_xy holds the box terms; db.l_wh is not used.
-__global__ __launch_bounds__(256) void ship_target_kernel(const float* __restrict__ tg, int T, const Level lv, const DemoBuf db) {
-    const int lane = threadIdx.x & 63, wpb = blockDim.x >> 6;
-    const int C = lv.K - 5;
-    for (int t = blockIdx.x * wpb + (threadIdx.x >> 6); t < T; t += gridDim.x * wpb) {
-        const float fw = (float)lv.W, fh = (float)lv.H;
-        const float tx = tg[t * 6 + 2] * fw, ty = tg[t * 6 + 3] * fh, tw = tg[t * 6 + 4] * fw, th = tg[t * 6 + 5] * fh;
-        int best = 0;
-        float best_iou = -INFINITY;
-        for (int a = 0; a < lv.A; ++a) {  // wh_iou_batch (iou.py:177-189) + torch.max first index
-            const float inter = fminf(tw, lv.aw[a]) * fminf(th, lv.ah[a]);
-            const float iou = inter / (((tw * th) + (lv.aw[a] * lv.ah[a])) - inter + IOU_EPS);
-            if (iou > best_iou) { best_iou = iou; best = a; }
-        }
-        const float gxf = floorf(tx), gyf = floorf(ty);
-        const int b = (int)tg[t * 6], gx = (int)gxf, gy = (int)gyf, cls = (int)tg[t * 6 + 1];
-        const bool ok = b >= 0 && b < lv.B && gx >= 0 && gx < lv.W && gy >= 0 && gy < lv.H;  // reference: IndexError otherwise
-        if (!ok) {
-            if (lane == 0) { db.l_xy[t] = 0.f; db.l_cls[t] = 0.f; db.cell[t] = -1; }
-            continue;
-        }
-        const int64_t base = b * lv.sb + best * lv.sa + gy * lv.sy + gx * lv.sx;
-        float lsum = 0.f;
-        const float gcls = 1.f / ((float)T * (float)C);
-        for (int k = lane; k < C; k += 64) {
-            const float z = lv.data[base + (5 + k) * lv.sk];
-            const float tt = (k == cls) ? 1.f : 0.f;
-            lsum += bce_logits(z, tt);
-            if (lv.grad) atomicAdd(&lv.grad[base + (5 + k) * lv.sk], (sigm(z) - tt) * gcls);
-        }
-        lsum = wave_sum(lsum);
-        if (lane == 0) {
-            const float z0 = lv.data[base], z1 = lv.data[base + lv.sk], z2 = lv.data[base + 2 * lv.sk], z3 = lv.data[base + 3 * lv.sk];
-            const float sx = sigm(z0), sy = sigm(z1);
-            const float px = sx + gxf, py = sy + gyf;  // :65-69
-            const float pw = expf(z2) * lv.aw[best], ph = expf(z3) * lv.ah[best];
-            const BoxD pb = xywh2xyxy_d(dvar(px, 0), dvar(py, 1), dvar(pw, 2), dvar(ph, 3));
-            const BoxD tb = xywh2xyxy_d(dconst(tx), dconst(ty), dconst(tw), dconst(th));
-            const D4 ciou = ciou_d(pb, tb, IOU_EPS, 1, nullptr);  // :87
-            db.l_xy[t] = 1.f - ciou.v;
-            db.l_cls[t] = lsum;
-            db.cell[t] = ((b * lv.H + gy) * lv.W + gx) * lv.A + best;
-            if (lv.grad) {
-                const float gb = 1.f / (float)T;  // :88 mean over the targets
-                const float dpdz[4] = {sx * (1.f - sx), sy * (1.f - sy), pw, ph};
-#pragma unroll
-                for (int i = 0; i < 4; ++i) atomicAdd(&lv.grad[base + i * lv.sk], -(ciou.d[i] * dpdz[i]) * gb);
-            }
-        }
-    }
+// cell i of the demo's mask layout [B, H, W, A] (a innermost) and the offset of its channel 0 through the level's strides
+struct DemoCell {
+    int b, y, x, a;
+    int64_t base;
+};
+__device__ __forceinline__ DemoCell demo_cell(const Level& lv, int64_t i) {
+    DemoCell c;
+    c.a = (int)(i % lv.A); c.x = (int)((i / lv.A) % lv.W); c.y = (int)((i / ((int64_t)lv.A * lv.W)) % lv.H);
+    c.b = (int)(i / ((int64_t)lv.A * lv.W * lv.H));
+    c.base = c.b * lv.sb + c.a * lv.sa + c.y * lv.sy + c.x * lv.sx;
+    return c;
 }
 
 // ignore mask (lossv3.py:86-100): per predicted box, max IoU against the targets of its image > 0.5 -> -1
 __global__ __launch_bounds__(256) void demo_mask_kernel(const float* __restrict__ tg, const Level lv, const DemoBuf db) {
     const int64_t n = (int64_t)lv.B * lv.H * lv.W * lv.A;
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const int a = (int)(i % lv.A), x = (int)((i / lv.A) % lv.W), y = (int)((i / ((int64_t)lv.A * lv.W)) % lv.H);
-        const int b = (int)(i / ((int64_t)lv.A * lv.W * lv.H));
-        const int64_t base = b * lv.sb + a * lv.sa + y * lv.sy + x * lv.sx;
-        const float px = sigm(lv.data[base]) + (float)x, py = sigm(lv.data[base + lv.sk]) + (float)y;
-        const float pw = expf(lv.data[base + 2 * lv.sk]) * lv.aw[a], ph = expf(lv.data[base + 3 * lv.sk]) * lv.ah[a];
+        const DemoCell at = demo_cell(lv, i);
+        const int64_t base = at.base;
+        const float px = sigm(lv.data[base]) + (float)at.x, py = sigm(lv.data[base + lv.sk]) + (float)at.y;
+        const float pw = expf(lv.data[base + 2 * lv.sk]) * lv.aw[at.a], ph = expf(lv.data[base + 3 * lv.sk]) * lv.ah[at.a];
         const float ax1 = px - pw / 2, ay1 = py - ph / 2, ax2 = px + pw / 2, ay2 = py + ph / 2;
         const float area_a = (ax2 - ax1) * (ay2 - ay1);
         const float fw = (float)lv.W, fh = (float)lv.H;
         bool ignore = false;
-        const int s = db.img_start[b], c = db.img_count[b];
+        const int s = db.img_start[at.b], c = db.img_count[at.b];
         for (int j = 0; j < c; ++j) {
             const int t = db.perm[s + j];
             const float tx = tg[t * 6 + 2] * fw, ty = tg[t * 6 + 3] * fh, tw = tg[t * 6 + 4] * fw, th = tg[t * 6 + 5] * fh;
@@ -549,9 +540,7 @@ __global__ __launch_bounds__(256) void demo_conf_kernel(const Level lv, const De
     float acc = 0.f, cnt = 0.f;
     const float inv = pass ? 1.f / *db.nvalid : 0.f;
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const int a = (int)(i % lv.A), x = (int)((i / lv.A) % lv.W), y = (int)((i / ((int64_t)lv.A * lv.W)) % lv.H);
-        const int b = (int)(i / ((int64_t)lv.A * lv.W * lv.H));
-        const int64_t off = b * lv.sb + a * lv.sa + y * lv.sy + x * lv.sx + 4 * lv.sk;
+        const int64_t off = demo_cell(lv, i).base + 4 * lv.sk;
         const int mk = db.mask[i];
         if (pass == 0) {
             if (mk != -1) { acc += bce_logits(lv.data[off], (float)mk); cnt += 1.f; }
@@ -559,7 +548,7 @@ __global__ __launch_bounds__(256) void demo_conf_kernel(const Level lv, const De
             lv.grad[off] = mk != -1 ? (sigm(lv.data[off]) - (float)mk) * inv : 0.f;
         }
     }
-    if (pass == 0) {
+    if (pass == 0) {  // block_sum_store, twice-wide under one barrier
         acc = wave_sum(acc);
         cnt = wave_sum(cnt);
         if ((threadIdx.x & 63) == 0) { ws[0][threadIdx.x >> 6] = acc; ws[1][threadIdx.x >> 6] = cnt; }
@@ -570,47 +559,33 @@ __global__ __launch_bounds__(256) void demo_conf_kernel(const Level lv, const De
         }
     }
 }
-// per level: finish N_valid and the four partial losses; acc[5] accumulates across levels
+// per level: finish N_valid and the partial losses; acc[P + 1] accumulates across levels.  P per-target parts, {l_xy, l_wh, l_cls} over
+// {2T, 2T, T C} or {box, l_cls} over {T, T C}, then the objectness sum over N_valid; out = {total, parts...}
+template <int BOX>
 __global__ __launch_bounds__(256) void demo_level_final_kernel(const DemoBuf db, int T, int C, int blocks, double* acc, float* out,
                                                                int last) {
-    __shared__ double red[5][256];
-    double s[5] = {0, 0, 0, 0, 0};
-    for (int i = threadIdx.x; i < T; i += 256) { s[0] += db.l_xy[i]; s[1] += db.l_wh[i]; s[2] += db.l_cls[i]; }
-    for (int i = threadIdx.x; i < blocks; i += 256) { s[3] += db.conf_part[2 * i]; s[4] += db.conf_part[2 * i + 1]; }
-    for (int k = 0; k < 5; ++k) red[k][threadIdx.x] = s[k];
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int k = 0; k < 5; ++k) { s[k] = 0; for (int i = 0; i < 256; ++i) s[k] += red[k][i]; }
-        *db.nvalid = (float)s[4];
-        acc[0] += s[0] / (2.0 * T);
-        acc[1] += s[1] / (2.0 * T);
-        acc[2] += s[2] / ((double)T * C);
-        acc[3] += s[3] / s[4];
-        if (last) {
-            out[1] = (float)acc[0]; out[2] = (float)acc[1]; out[3] = (float)acc[2]; out[4] = (float)acc[3];
-            out[0] = (float)(acc[0] * 2.0 + acc[1] + acc[2] + acc[3]);
-        }
+    constexpr int P = BOX == BOX_XYWH ? 3 : 2, N = P + 2;
+    __shared__ double red[N][256];
+    double s[N] = {};
+    for (int i = threadIdx.x; i < T; i += 256) {
+        s[0] += db.l_xy[i];
+        if constexpr (BOX == BOX_XYWH) s[1] += db.l_wh[i];
+        s[P - 1] += db.l_cls[i];
     }
-}
-
-// the same finish for the ship demo's three parts (box terms in db.l_xy): acc[3] accumulates across levels
-__global__ __launch_bounds__(256) void ship_level_final_kernel(const DemoBuf db, int T, int C, int blocks, double* acc, float* out,
-                                                               int last) {
-    __shared__ double red[4][256];
-    double s[4] = {0, 0, 0, 0};
-    for (int i = threadIdx.x; i < T; i += 256) { s[0] += db.l_xy[i]; s[1] += db.l_cls[i]; }
-    for (int i = threadIdx.x; i < blocks; i += 256) { s[2] += db.conf_part[2 * i]; s[3] += db.conf_part[2 * i + 1]; }
-    for (int k = 0; k < 4; ++k) red[k][threadIdx.x] = s[k];
+    for (int i = threadIdx.x; i < blocks; i += 256) { s[P] += db.conf_part[2 * i]; s[P + 1] += db.conf_part[2 * i + 1]; }
+    for (int k = 0; k < N; ++k) red[k][threadIdx.x] = s[k];
     __syncthreads();
     if (threadIdx.x == 0) {
-        for (int k = 0; k < 4; ++k) { s[k] = 0; for (int i = 0; i < 256; ++i) s[k] += red[k][i]; }
-        *db.nvalid = (float)s[3];
-        acc[0] += s[0] / (double)T;
-        acc[1] += s[1] / ((double)T * C);
-        acc[2] += s[2] / s[3];
+        for (int k = 0; k < N; ++k) { s[k] = 0; for (int i = 0; i < 256; ++i) s[k] += red[k][i]; }
+        *db.nvalid = (float)s[P + 1];
+        acc[0] += s[0] / (BOX == BOX_XYWH ? 2.0 * T : (double)T);
+        if constexpr (BOX == BOX_XYWH) acc[1] += s[1] / (2.0 * T);
+        acc[P - 1] += s[P - 1] / ((double)T * C);
+        acc[P] += s[P] / s[P + 1];
         if (last) {
             out[1] = (float)acc[0]; out[2] = (float)acc[1]; out[3] = (float)acc[2];
-            out[0] = (float)(acc[0] + acc[1] + acc[2]);
+            if constexpr (BOX == BOX_XYWH) out[4] = (float)acc[3];
+            out[0] = BOX == BOX_XYWH ? (float)(acc[0] * 2.0 + acc[1] + acc[2] + acc[3]) : (float)(acc[0] + acc[1] + acc[2]);
         }
     }
 }
@@ -778,10 +753,7 @@ __global__ __launch_bounds__(256) void bce_kernel(const float* __restrict__ y, c
             grad[i] = wi * dldp * (already_sigmoid ? 1.f : p * (1.f - p));
         }
     }
-    acc = wave_sum(acc);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) partial[blockIdx.x] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+    block_sum_store(acc, wsum, partial + blockIdx.x);
 }
 __global__ __launch_bounds__(256) void bce_final_kernel(const float* __restrict__ partial, int nblocks, double denom, float* out) {
     __shared__ double red[256];
@@ -842,10 +814,7 @@ __global__ __launch_bounds__(256) void smooth_l1_kernel(const float* __restrict_
         acc += ad < 1.f ? 0.5f * d * d : ad - 0.5f;
         if (grad) grad[i] = (ad < 1.f ? d : (d > 0.f ? 1.f : -1.f)) * inv;
     }
-    acc = wave_sum(acc);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) partial[blockIdx.x] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+    block_sum_store(acc, wsum, partial + blockIdx.x);
 }
 
 inline int64_t align256(int64_t x) { return (x + 255) & ~255ll; }
@@ -860,6 +829,8 @@ struct Carver {
     }
 };
 constexpr int CONF_BLOCKS = 1024;
+// grid of a grid-stride kernel with 256 threads per block over n elements
+inline int capped_blocks(int64_t n, int cap) { return (int)((n + 255) / 256 < cap ? (n + 255) / 256 : cap); }
 
 MatchBuf carve_match(Carver& c, int cap) {
     MatchBuf m;
@@ -984,7 +955,7 @@ int fva_yolov3_loss_dp(const float* targets, int32_t T, const fva_head_level* le
                                cls_l, ratio_box, ratio_conf, ratio_cls, norm_counts ? norm_counts + l : nullptr, norm_batch);
             FVA_LAUNCH_CHECK("match_loss_kernel");
         }
-        const int cblocks = (int)((ncell + 255) / 256 < CONF_BLOCKS ? (ncell + 255) / 256 : CONF_BLOCKS);
+        const int cblocks = capped_blocks(ncell, CONF_BLOCKS);
         hipLaunchKernelGGL(conf_kernel, dim3(cblocks), dim3(256), 0, s, lv, (const int32_t*)cellmatch, (const float*)iou, conf_part,
                            ratio_conf);
         FVA_LAUNCH_CHECK("conf_kernel");
@@ -1015,33 +986,37 @@ int64_t fva_demo_loss_workspace(int32_t T, const fva_head_level* levels, int32_t
     return c.off;
 }
 
-int fva_demo_loss(const float* targets, int32_t T, const fva_head_level* levels, int32_t nlevels, float* loss_out, void* workspace,
-                  int64_t workspace_bytes, void* stream) {
+// both demo losses: arguments, then every level, then the workspace size are checked before the first device call
+static int demo_loss(DemoBox box, const char* who, const float* targets, int32_t T, const fva_head_level* levels, int32_t nlevels,
+                     float* loss_out, void* workspace, int64_t workspace_bytes, void* stream) {
     if (!levels || nlevels < 1 || nlevels > 4 || !loss_out || !workspace || !targets || T < 1)
-        return fva_fail(FVA_ERR_ARG, "fva_demo_loss: bad argument (the reference needs >= 1 target)");
-    if (workspace_bytes < fva_demo_loss_workspace(T, levels, nlevels)) return fva_fail(FVA_ERR_WORKSPACE, "fva_demo_loss: workspace too small");
+        return fva_fail(FVA_ERR_ARG, "%s: bad argument (the reference needs >= 1 target)", who);
+    for (int l = 0; l < nlevels; ++l) {
+        int rc = check_level(levels[l], who);
+        if (rc) return rc;
+    }
+    if (workspace_bytes < fva_demo_loss_workspace(T, levels, nlevels)) return fva_fail(FVA_ERR_WORKSPACE, "%s: workspace too small", who);
     hipStream_t s = (hipStream_t)stream;
     Carver c{(char*)workspace};
     double* acc = c.take<double>(8);
-    if (hipMemsetAsync(acc, 0, 64, s) != hipSuccess) return fva_fail(FVA_ERR_LAUNCH, "fva_demo_loss: memset failed");
+    if (hipMemsetAsync(acc, 0, 64, s) != hipSuccess) return fva_fail(FVA_ERR_LAUNCH, "%s: memset failed", who);
+    const auto target_kernel = box == BOX_CIOU ? demo_target_kernel<BOX_CIOU> : demo_target_kernel<BOX_XYWH>;
+    const auto level_final_kernel = box == BOX_CIOU ? demo_level_final_kernel<BOX_CIOU> : demo_level_final_kernel<BOX_XYWH>;
     for (int l = 0; l < nlevels; ++l) {
-        int rc = check_level(levels[l], "fva_demo_loss");
-        if (rc) return rc;
         const Level lv = to_level(levels[l]);
         const DemoBuf db = carve_demo(c, T, levels[l]);
-        const int64_t n = (int64_t)lv.B * lv.H * lv.W * lv.A;
-        const int blocks = (int)((n + 255) / 256 < CONF_BLOCKS ? (n + 255) / 256 : CONF_BLOCKS);
+        const int blocks = capped_blocks((int64_t)lv.B * lv.H * lv.W * lv.A, CONF_BLOCKS);
         hipLaunchKernelGGL(demo_group_kernel, dim3(1), dim3(256), 2 * lv.B * 4, s, targets, T, lv.B, db.img_start, db.img_count, db.perm);
         FVA_LAUNCH_CHECK("demo_group_kernel");
         hipLaunchKernelGGL(demo_mask_kernel, dim3(blocks), dim3(256), 0, s, targets, lv, db);
         FVA_LAUNCH_CHECK("demo_mask_kernel");
-        hipLaunchKernelGGL(demo_target_kernel, dim3(cdiv(T, 4) < 2048 ? cdiv(T, 4) : 2048), dim3(256), 0, s, targets, T, lv, db);
+        hipLaunchKernelGGL(target_kernel, dim3(cdiv(T, 4) < 2048 ? cdiv(T, 4) : 2048), dim3(256), 0, s, targets, T, lv, db);
         FVA_LAUNCH_CHECK("demo_target_kernel");
         hipLaunchKernelGGL(demo_positive_kernel, dim3(cdiv(T, 256)), dim3(256), 0, s, T, db);
         FVA_LAUNCH_CHECK("demo_positive_kernel");
         hipLaunchKernelGGL(demo_conf_kernel, dim3(blocks), dim3(256), 0, s, lv, db, 0);
         FVA_LAUNCH_CHECK("demo_conf_kernel");
-        hipLaunchKernelGGL(demo_level_final_kernel, dim3(1), dim3(256), 0, s, db, T, lv.K - 5, blocks, acc, loss_out, l == nlevels - 1 ? 1 : 0);
+        hipLaunchKernelGGL(level_final_kernel, dim3(1), dim3(256), 0, s, db, T, lv.K - 5, blocks, acc, loss_out, l == nlevels - 1 ? 1 : 0);
         FVA_LAUNCH_CHECK("demo_level_final_kernel");
         if (lv.grad) {
             hipLaunchKernelGGL(demo_conf_kernel, dim3(blocks), dim3(256), 0, s, lv, db, 1);
@@ -1051,46 +1026,18 @@ int fva_demo_loss(const float* targets, int32_t T, const fva_head_level* levels,
     return FVA_OK;
 }
 
+int fva_demo_loss(const float* targets, int32_t T, const fva_head_level* levels, int32_t nlevels, float* loss_out, void* workspace,
+                  int64_t workspace_bytes, void* stream) {
+    return demo_loss(BOX_XYWH, "fva_demo_loss", targets, T, levels, nlevels, loss_out, workspace, workspace_bytes, stream);
+}
+
 int64_t fva_demo_ciou_loss_workspace(int32_t T, const fva_head_level* levels, int32_t nlevels) {
     return fva_demo_loss_workspace(T, levels, nlevels);
 }
 
 int fva_demo_ciou_loss(const float* targets, int32_t T, const fva_head_level* levels, int32_t nlevels, float* loss_out, void* workspace,
                        int64_t workspace_bytes, void* stream) {
-    if (!levels || nlevels < 1 || nlevels > 4 || !loss_out || !workspace || !targets || T < 1)
-        return fva_fail(FVA_ERR_ARG, "fva_demo_ciou_loss: bad argument (the reference needs >= 1 target)");
-    for (int l = 0; l < nlevels; ++l) {  // every level is checked before the first device call
-        int rc = check_level(levels[l], "fva_demo_ciou_loss");
-        if (rc) return rc;
-    }
-    if (workspace_bytes < fva_demo_ciou_loss_workspace(T, levels, nlevels)) return fva_fail(FVA_ERR_WORKSPACE, "fva_demo_ciou_loss: workspace too small");
-    hipStream_t s = (hipStream_t)stream;
-    Carver c{(char*)workspace};
-    double* acc = c.take<double>(8);
-    if (hipMemsetAsync(acc, 0, 64, s) != hipSuccess) return fva_fail(FVA_ERR_LAUNCH, "fva_demo_ciou_loss: memset failed");
-    for (int l = 0; l < nlevels; ++l) {
-        const Level lv = to_level(levels[l]);
-        const DemoBuf db = carve_demo(c, T, levels[l]);
-        const int64_t n = (int64_t)lv.B * lv.H * lv.W * lv.A;
-        const int blocks = (int)((n + 255) / 256 < CONF_BLOCKS ? (n + 255) / 256 : CONF_BLOCKS);
-        hipLaunchKernelGGL(demo_group_kernel, dim3(1), dim3(256), 2 * lv.B * 4, s, targets, T, lv.B, db.img_start, db.img_count, db.perm);
-        FVA_LAUNCH_CHECK("demo_group_kernel");
-        hipLaunchKernelGGL(demo_mask_kernel, dim3(blocks), dim3(256), 0, s, targets, lv, db);
-        FVA_LAUNCH_CHECK("demo_mask_kernel");
-        hipLaunchKernelGGL(ship_target_kernel, dim3(cdiv(T, 4) < 2048 ? cdiv(T, 4) : 2048), dim3(256), 0, s, targets, T, lv, db);
-        FVA_LAUNCH_CHECK("ship_target_kernel");
-        hipLaunchKernelGGL(demo_positive_kernel, dim3(cdiv(T, 256)), dim3(256), 0, s, T, db);
-        FVA_LAUNCH_CHECK("demo_positive_kernel");
-        hipLaunchKernelGGL(demo_conf_kernel, dim3(blocks), dim3(256), 0, s, lv, db, 0);
-        FVA_LAUNCH_CHECK("demo_conf_kernel");
-        hipLaunchKernelGGL(ship_level_final_kernel, dim3(1), dim3(256), 0, s, db, T, lv.K - 5, blocks, acc, loss_out, l == nlevels - 1 ? 1 : 0);
-        FVA_LAUNCH_CHECK("ship_level_final_kernel");
-        if (lv.grad) {
-            hipLaunchKernelGGL(demo_conf_kernel, dim3(blocks), dim3(256), 0, s, lv, db, 1);
-            FVA_LAUNCH_CHECK("demo_conf_kernel");
-        }
-    }
-    return FVA_OK;
+    return demo_loss(BOX_CIOU, "fva_demo_ciou_loss", targets, T, levels, nlevels, loss_out, workspace, workspace_bytes, stream);
 }
 
 int fva_scale_head_groups(const fva_head_level* level, const float* g_box, const float* g_cls, const float* g_conf, void* stream) {
@@ -1099,9 +1046,7 @@ int fva_scale_head_groups(const fva_head_level* level, const float* g_box, const
     if (rc) return rc;
     const Level lv = to_level(*level);
     const int64_t n = (int64_t)lv.B * lv.A * lv.H * lv.W * lv.K;
-    int64_t g = (n + 255) / 256;
-    if (g > 2048) g = 2048;
-    hipLaunchKernelGGL(scale_head_groups_kernel, dim3((int)g), dim3(256), 0, (hipStream_t)stream, lv, g_box, g_cls, g_conf, lv.sk == 1 ? 1 : 0);
+    hipLaunchKernelGGL(scale_head_groups_kernel, dim3(capped_blocks(n, 2048)), dim3(256), 0, (hipStream_t)stream, lv, g_box, g_cls, g_conf, lv.sk == 1 ? 1 : 0);
     FVA_LAUNCH_CHECK("scale_head_groups_kernel");
     return FVA_OK;
 }
@@ -1123,7 +1068,7 @@ int fva_bce_loss(const float* y, const int64_t* label, const float* dense_target
     if (!y || (!label && !dense_target) || !loss_out || !workspace || numel < 1 || C < 1 || numel % C)
         return fva_fail(FVA_ERR_ARG, "fva_bce_loss: bad argument");
     if (weights && weights_numel != 1 && weights_numel != numel) return fva_fail(FVA_ERR_ARG, "fva_bce_loss: weights must have 1 or numel entries");
-    const int blocks = (int)((numel + 255) / 256 < CONF_BLOCKS ? (numel + 255) / 256 : CONF_BLOCKS);
+    const int blocks = capped_blocks(numel, CONF_BLOCKS);
     hipLaunchKernelGGL(bce_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, y, label, dense_target, weights, weights_numel, numel, C,
                        already_sigmoid, workspace, grad);
     FVA_LAUNCH_CHECK("bce_kernel");
@@ -1145,7 +1090,7 @@ int fva_row_loss(const float* logits, const int64_t* labels, int32_t R, int32_t 
 
 int fva_smooth_l1(const float* pred, const float* target, int64_t n, float* loss_out, float* grad, float* workspace, void* stream) {
     if (!pred || !target || !loss_out || !workspace || n < 1) return fva_fail(FVA_ERR_ARG, "fva_smooth_l1: bad argument");
-    const int blocks = (int)((n + 255) / 256 < CONF_BLOCKS ? (n + 255) / 256 : CONF_BLOCKS);
+    const int blocks = capped_blocks(n, CONF_BLOCKS);
     hipLaunchKernelGGL(smooth_l1_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, pred, target, n, workspace, grad);
     FVA_LAUNCH_CHECK("smooth_l1_kernel");
     hipLaunchKernelGGL(bce_final_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)workspace, blocks, (double)n, loss_out);
@@ -1157,8 +1102,8 @@ int fva_iou_pairwise(int kind, int mode, int variant, const float* a, const floa
                      void* stream) {
     if (!a || !b || !out || kind < 0 || kind > 3 || mode < 0 || mode > 2) return fva_fail(FVA_ERR_ARG, "fva_iou_pairwise: bad argument");
     if (N == 0) return FVA_OK;
-    hipLaunchKernelGGL(iou_pair_kernel, dim3((int)((N + 255) / 256 < 2048 ? (N + 255) / 256 : 2048)), dim3(256), 0, (hipStream_t)stream,
-                       kind, mode, variant, a, b, out, grad_a, N, eps);
+    hipLaunchKernelGGL(iou_pair_kernel, dim3(capped_blocks(N, 2048)), dim3(256), 0, (hipStream_t)stream, kind, mode, variant, a, b, out,
+                       grad_a, N, eps);
     FVA_LAUNCH_CHECK("iou_pair_kernel");
     return FVA_OK;
 }
@@ -1167,8 +1112,8 @@ int fva_iou_batch(int kind, int mode, int variant, const float* a, const float* 
                   void* stream) {
     if (!a || !b || !out || kind < 0 || kind > 3 || mode < 0 || mode > 2) return fva_fail(FVA_ERR_ARG, "fva_iou_batch: bad argument");
     if (N * M == 0) return FVA_OK;
-    hipLaunchKernelGGL(iou_batch_kernel, dim3((int)((N * M + 255) / 256 < 2048 ? (N * M + 255) / 256 : 2048)), dim3(256), 0,
-                       (hipStream_t)stream, kind, mode, variant, a, b, out, N, M, eps);
+    hipLaunchKernelGGL(iou_batch_kernel, dim3(capped_blocks(N * M, 2048)), dim3(256), 0, (hipStream_t)stream, kind, mode, variant, a, b, out,
+                       N, M, eps);
     FVA_LAUNCH_CHECK("iou_batch_kernel");
     return FVA_OK;
 }

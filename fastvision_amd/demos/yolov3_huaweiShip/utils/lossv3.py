@@ -8,10 +8,9 @@ disjoint channel groups of it (k < 4 box, k == 4 objectness, k >= 5 class) the b
 scalar (``fva_scale_head_groups``; no traffic for ``(box + cls + conf).backward()``).
 """
 import torch
-import torch.nn as nn
 
-from .... import _lib
-from ....ops import _p, _stream, require_gpu, scale_head_group_grads
+from ....loss.demo_loss import DemoComputeLoss, demo_loss_forward
+from ....ops import scale_head_group_grads
 
 __all__ = ['ComputeLoss']
 
@@ -19,39 +18,7 @@ __all__ = ['ComputeLoss']
 class _ShipLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, targets, anchors, *layers):
-        need = any(ctx.needs_input_grad[2:])
-        hs, grads = [], []
-        levels = (_lib.HeadLevel * len(layers))()
-        for i, raw in enumerate(layers):
-            h = raw.detach()
-            if h.dtype != torch.float32:
-                h = h.float()
-            B, ch, gh, gw = h.shape
-            A = len(anchors[i])
-            K = ch // A
-            g = None
-            if need:
-                g = torch.zeros_like(h)
-                if g.stride() != h.stride():
-                    h = h.contiguous()
-                    g = torch.zeros_like(h)
-            sb, sc, sy, sx = h.stride()
-            lv = levels[i]
-            lv.data, lv.grad = h.data_ptr(), (g.data_ptr() if g is not None else None)
-            lv.sb, lv.sa, lv.sy, lv.sx, lv.sk = sb, K * sc, sy, sx, sc      # channel c = a*K + k  (lossv3.py:43)
-            lv.B, lv.A, lv.H, lv.W, lv.K = B, A, gh, gw, K
-            for j, (w, hh) in enumerate(anchors[i]):
-                lv.anchor_w[j], lv.anchor_h[j] = w, hh
-            lv.stride = 1.0
-            hs.append(h)
-            grads.append(g)
-        T = targets.shape[0]
-        lib = _lib.load()
-        wsb = lib.fva_demo_ciou_loss_workspace(T, levels, len(hs))
-        ws = torch.empty(wsb, dtype=torch.uint8, device=hs[0].device)
-        out = torch.empty(4, dtype=torch.float32, device=hs[0].device)
-        _lib.call('fva_demo_ciou_loss', _p(targets), T, levels, len(hs), _p(out), _p(ws), wsb, _stream())
-        ctx.grads, ctx.dtypes, ctx.anchors_per_level = grads, [l.dtype for l in layers], [len(a) for a in anchors]
+        out = demo_loss_forward(ctx, 'fva_demo_ciou_loss', 4, targets, anchors, layers)
         parts = out[1:4].clone()
         ctx.mark_non_differentiable(parts)
         return out[1:2].clone(), out[2:3].clone(), out[3:4].clone(), parts
@@ -61,24 +28,10 @@ class _ShipLossFn(torch.autograd.Function):
         return (None, None, *scale_head_group_grads(ctx, g_box, g_cls, g_conf))
 
 
-class ComputeLoss(nn.Module):
-    def __init__(self):
-        super().__init__()
-        self.last_parts = None
-        self._anchors = None                     # (key, host copy): reading model.anchors is a device sync, and not allowed inside a graph capture
-
-    def get_model(self, model):
-        return model.module if hasattr(model, 'module') else model
+class ComputeLoss(DemoComputeLoss):
+    empty_targets = 'ComputeLoss needs at least one target (the reference fails on an empty batch too, lossv3.py:88)'
 
     def forward(self, predict_layers, target_all, model):
-        model = self.get_model(model)
-        require_gpu(predict_layers[0], 'ComputeLoss')
-        key = tuple((a.data_ptr(), a._version) for a in model.anchors)
-        if self._anchors is None or self._anchors[0] != key:
-            self._anchors = (key, [[(float(w), float(h)) for w, h in a.reshape(-1, 2).tolist()] for a in model.anchors])   # feature scale
-        anchors = self._anchors[1]
-        if target_all.shape[0] == 0:
-            raise RuntimeError('ComputeLoss needs at least one target (the reference fails on an empty batch too, lossv3.py:88)')
-        tg = target_all.detach().to(device=predict_layers[0].device, dtype=torch.float32).contiguous()
+        tg, anchors = self._inputs(predict_layers, target_all, model)
         loss_box, loss_cls, loss_conf, self.last_parts = _ShipLossFn.apply(tg, anchors, *predict_layers)      # last_parts = (box, cls, conf)
         return loss_box, loss_cls, loss_conf

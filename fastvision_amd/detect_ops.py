@@ -21,17 +21,6 @@ NMS_DEMO_BATCH = dict(box_mode=0, score_mode=0, rethreshold=1, class_gap=4096.0,
 MASK_BYTES_PER_CALL = 2 << 30   # images are processed in groups whose suppression bitmaps fit this much HBM
 
 
-def _level(h, anchors, stride):
-    lv = _lib.HeadLevel()
-    lv.data, lv.grad = h.data_ptr(), None
-    lv.sb, lv.sa, lv.sy, lv.sx, lv.sk = h.stride()
-    lv.B, lv.A, lv.H, lv.W, lv.K = h.shape
-    for i, (w, hh) in enumerate(anchors):
-        lv.anchor_w[i], lv.anchor_h[i] = float(w), float(hh)
-    lv.stride = float(stride)
-    return lv
-
-
 def yolo_decode(heads, anchors, strides, variant=0, letterbox=None):
     """heads: fp32 CUDA tensors [B,A,H,W,K] (any strides) per level; anchors: per level a sequence of (w, h);
     returns [B, sum A*H*W, K] fp32.  variant / letterbox: see fva_yolo_decode in include/fastvision_amd.h."""
@@ -40,7 +29,7 @@ def yolo_decode(heads, anchors, strides, variant=0, letterbox=None):
     levels = (_lib.HeadLevel * len(heads))()
     rows = 0
     for i, h in enumerate(heads):
-        levels[i] = _level(h, anchors[i], strides[i])
+        levels[i] = _lib.head_level_5d(h, None, anchors[i], strides[i])
         rows += h.shape[1] * h.shape[2] * h.shape[3]
     B, K = heads[0].shape[0], heads[0].shape[4]
     out = torch.empty(B, rows, K, dtype=torch.float32, device=heads[0].device)

@@ -11,21 +11,11 @@ import torch
 import torch.nn as nn
 
 from .. import _lib
-from ..ops import _p, _stream, require_gpu
+from ..ops import _p, _stream, head_grad_buffer, require_gpu
 
 __all__ = ['Yolov3Loss']
 
-
-def make_level(h, grad, anchors_px, stride):
-    """fva_head_level for a head tensor [B,A,H,W,K] of any strides (and a gradient buffer with the same strides)."""
-    lv = _lib.HeadLevel()
-    lv.data, lv.grad = h.data_ptr(), (grad.data_ptr() if grad is not None else None)
-    lv.sb, lv.sa, lv.sy, lv.sx, lv.sk = h.stride()
-    lv.B, lv.A, lv.H, lv.W, lv.K = h.shape
-    for i, (w, hh) in enumerate(anchors_px):
-        lv.anchor_w[i], lv.anchor_h[i] = w, hh
-    lv.stride = float(stride)
-    return lv
+make_level = _lib.head_level_5d     # (h [B,A,H,W,K], grad, anchors_px, stride)
 
 
 def _as_f32(h):
@@ -61,14 +51,9 @@ class _Yolov3LossFn(torch.autograd.Function):
         grads = []
         levels = (_lib.HeadLevel * len(hs))()
         for i, h in enumerate(hs):
-            g = None
-            if need:
-                g = torch.zeros_like(h)                     # preserve_format keeps the (dense) strides of h
-                if g.stride() != h.stride():
-                    hs[i] = h = h.contiguous()
-                    g = torch.zeros_like(h)
+            hs[i], g = head_grad_buffer(h, need)
             grads.append(g)
-            levels[i] = make_level(h, g, anchors[i], strides[i])
+            levels[i] = make_level(hs[i], g, anchors[i], strides[i])
         T = targets.shape[0]
         lib = _lib.load()
         wsb = lib.fva_yolov3_loss_workspace(T, levels, len(hs))
@@ -147,12 +132,7 @@ class Yolov3Loss(nn.Module):
             anc = torch.empty((cap, 2), dtype=torch.float32, device=dev)
             shape5 = (pre.shape[0], A, pre.shape[2], pre.shape[3], pre.shape[4])
             dummy = torch.empty(0, device=dev)
-            lv = _lib.HeadLevel()
-            lv.data = dummy.data_ptr() or 1
-            lv.B, lv.A, lv.H, lv.W, lv.K = shape5
-            for i, (w, h) in enumerate(self._anchors_px[lvl]):
-                lv.anchor_w[i], lv.anchor_h[i] = w, h
-            lv.stride = float(self.backbone_stride_levels[lvl])
+            lv = _lib.head_level(dummy.data_ptr() or 1, None, shape5, (0,) * 5, self._anchors_px[lvl], self.backbone_stride_levels[lvl])
             mo = _lib.MatchOut(count.data_ptr(), b.data_ptr(), gx.data_ptr(), gy.data_ptr(), a.data_ptr(), cls.data_ptr(),
                                xywh.data_ptr(), anc.data_ptr())
             _lib.call('fva_yolov3_match', _p(tg) if T else C.c_void_p(0), T, C.byref(lv), C.byref(mo), _stream())

@@ -558,6 +558,18 @@ def _in_place_scalar(gout, g):
             and g.storage_offset() == 0 and g.untyped_storage().nbytes() == g.numel() * 4 and g.data_ptr() % 16 == 0)
 
 
+def head_grad_buffer(h, need):
+    """(h, g) for a fused loss: g, a zeroed gradient buffer with the strides of h (None unless ``need``); a head whose strides
+    zeros_like cannot reproduce (not dense) is made contiguous first."""
+    if not need:
+        return h, None
+    g = torch.zeros_like(h)                     # preserve_format keeps the (dense) strides of h
+    if g.stride() != h.stride():
+        h = h.contiguous()
+        g = torch.zeros_like(h)
+    return h, g
+
+
 def scale_loss_grads(ctx, gout):
     """Chain rule of the fused losses (loss.Yolov3Loss, the demo's ComputeLoss): their forward pass already filled ctx.grads with
     d loss / d head; backward multiplies by the upstream scalar.  For fp32 buffers that this package allocated the multiply runs IN
@@ -592,17 +604,10 @@ def scale_head_group_grads(ctx, g_box, g_cls, g_conf):
         if g is None:
             res.append(None)
             continue
-        B, ch, H, W = g.shape
-        K = ch // A
         if all(_in_place_scalar(s, g) for s in (g_box, g_cls, g_conf)):
-            sb, sc, sy, sx = g.stride()
-            lv = _lib.HeadLevel()
-            lv.data = lv.grad = g.data_ptr()
-            lv.sb, lv.sa, lv.sy, lv.sx, lv.sk = sb, K * sc, sy, sx, sc
-            lv.B, lv.A, lv.H, lv.W, lv.K = B, A, H, W, K
-            lv.stride = 1.0
-            _lib.call('fva_scale_head_groups', C.byref(lv), _p(g_box), _p(g_cls), _p(g_conf), _stream())
+            _lib.call('fva_scale_head_groups', C.byref(_lib.head_level_nchw(g, g, A)), _p(g_box), _p(g_cls), _p(g_conf), _stream())
         else:
+            K = g.shape[1] // A
             g5 = g.unflatten(1, (A, K))
             out = torch.empty_like(g)
             o5 = out.unflatten(1, (A, K))

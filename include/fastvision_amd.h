@@ -400,17 +400,20 @@ int fva_row_loss(const float* logits, const int64_t* labels, int32_t R, int32_t 
                  float* workspace, void* stream);
 int fva_smooth_l1(const float* pred, const float* target, int64_t n, float* loss_out, float* grad, float* workspace, void* stream);
 
-/* Demo loss (demos/yolov3_u/utils/lossv3.py:18-119): best-anchor assignment, BCE/MSE/BCE terms, IoU>0.5
- * ignore mask, masked objectness BCE.  level.anchor_* are FEATURE-scale here and level.stride is unused.
- * loss_out[5] = {total, xy, wh, cls, conf} (unweighted parts, as the reference prints them). */
+/* The two demo losses are one pipeline with two box terms: best-anchor assignment, class BCE-with-logits (mean over T * C), IoU>0.5
+ * ignore mask and masked objectness BCE are shared.  Both check their arguments, every level and the workspace size before the first
+ * device call; T >= 1.  level.anchor_* are FEATURE-scale here and level.stride is unused.
+ *
+ * fva_demo_loss (demos/yolov3_u/utils/lossv3.py:18-119): box term BCE(xy) + MSE(wh).
+ * loss_out[5] = {total, xy, wh, cls, conf} (unweighted parts, as the reference prints them; total = 2 xy + wh + cls + conf). */
 int fva_demo_loss(const float* targets, int32_t T, const fva_head_level* levels, int32_t nlevels, float* loss_out,
                   void* workspace, int64_t workspace_bytes, void* stream);
 int64_t fva_demo_loss_workspace(int32_t T, const fva_head_level* levels, int32_t nlevels);
 
-/* Loss of the second demo (demos/yolov3_huaweiShip/utils/lossv3.py:35-120): the same assignment, ignore mask and masked objectness BCE;
- * the box term is mean over T of 1 - CIoU(pred, target; 'xywh', eps 1e-7), pred = (sigmoid(z_xy) + cell, exp(z_wh) * anchor), with the
- * demo's CIoU (fva_iou_pairwise kind 3, variant 1); class term BCE-with-logits, mean over T * C.  Arguments and argument rules as
- * fva_demo_loss.  loss_out[4] = {box + cls + conf, box, cls, conf}; level.grad receives d (box + cls + conf) / d head: the box part in
+/* fva_demo_ciou_loss (demos/yolov3_huaweiShip/utils/lossv3.py:35-120): the same pipeline with the box term
+ * mean over T of 1 - CIoU(pred, target; 'xywh', eps 1e-7), pred = (sigmoid(z_xy) + cell, exp(z_wh) * anchor), with the
+ * demo's CIoU (fva_iou_pairwise kind 3, variant 1).  Arguments and argument rules as fva_demo_loss; the workspace size is the same.
+ * loss_out[4] = {box + cls + conf, box, cls, conf}; level.grad receives d (box + cls + conf) / d head: the box part in
  * channels 0..3 of the matched (cell, anchor), the objectness part in channel 4, the class part in channels 5.. */
 int fva_demo_ciou_loss(const float* targets, int32_t T, const fva_head_level* levels, int32_t nlevels, float* loss_out,
                        void* workspace, int64_t workspace_bytes, void* stream);

@@ -49,6 +49,37 @@ def test_argument_errors_are_reported_not_crashed(built):
     assert b'another accumulator' in lib.fva_last_error()
 
 
+def test_head_level_builders_fill_every_field():
+    """fva_head_level from a 5-D head [B,A,H,W,K] and from a 4-D [B, A*K, H, W] tensor split as c = a*K + k, against values written out by
+    hand (H != W: a swap of sy / sx shows)."""
+    from fastvision_amd import _lib
+    B, A, H, W, K = 2, 3, 2, 3, 6
+    anchors = [(10.0, 13.0), (16.0, 30.0), (33.0, 23.0)]
+
+    def check(lv, data, grad, strides, stride):
+        assert (lv.data, lv.grad) == (data, grad)
+        assert (lv.sb, lv.sa, lv.sy, lv.sx, lv.sk) == strides
+        assert (lv.B, lv.A, lv.H, lv.W, lv.K) == (2, 3, 2, 3, 6)
+        assert list(lv.anchor_w) == [10.0, 16.0, 33.0, 0.0, 0.0, 0.0, 0.0, 0.0]            # unused slots are zero
+        assert list(lv.anchor_h) == [13.0, 30.0, 23.0, 0.0, 0.0, 0.0, 0.0, 0.0]
+        assert lv.stride == stride
+
+    h = torch.zeros(B, A, H, W, K)
+    g = torch.zeros_like(h)
+    check(_lib.head_level_5d(h, g, anchors, 8), h.data_ptr(), g.data_ptr(), (108, 36, 18, 6, 1), 8.0)
+    v = torch.zeros(B, H, W, A, K).permute(0, 3, 1, 2, 4)                                   # [B,A,H,W,K] view of a [B,H,W,A,K] buffer
+    check(_lib.head_level_5d(v, None, anchors, 32), v.data_ptr(), None, (108, 6, 54, 18, 1), 32.0)      # grad=None: a null pointer
+    n = torch.zeros(B, A * K, H, W)
+    gn = torch.zeros_like(n)
+    assert n.stride(1) == 6
+    check(_lib.head_level_nchw(n, gn, A, anchors), n.data_ptr(), gn.data_ptr(), (108, 6 * 6, 3, 1, 6), 1.0)    # sa = K * stride(1), sk = stride(1)
+    c = n.contiguous(memory_format=torch.channels_last)
+    assert c.stride() == (108, 1, 54, 18)
+    check(_lib.head_level_nchw(c, None, A, anchors), c.data_ptr(), None, (108, 6 * 1, 54, 18, 1), 1.0)
+    bare = _lib.head_level(16, None, (B, A, H, W, K), (0,) * 5)
+    assert bare.data == 16 and bare.grad is None and list(bare.anchor_w) == [0.0] * 8 and bare.stride == 1.0
+
+
 def test_modules_mirror_reference_keys_and_seeded_init():
     from fastvision_amd.classfication.models import darknet53
     from fastvision_amd.demos.yolov3_u.models import YoloV3

@@ -119,6 +119,20 @@ def test_argument_errors_are_reported_before_any_pointer_is_read(built):
     assert b'rows_per_image' in lib.fva_last_error()
 
 
+@pytest.mark.parametrize('name', ['fva_demo_loss', 'fva_demo_ciou_loss'])
+def test_a_bad_later_level_is_refused_before_anything_is_enqueued(built, name):
+    """Two levels, the first valid, the second with K = 5; every pointer is 16 and the workspace is large enough.  The level check of
+    level 1 has to speak before the first device call (the accumulator memset), with or without a GPU."""
+    lib = built.load()
+    p = C.c_void_p(16)
+    levels = (built.HeadLevel * 2)(_level(built), _level(built, K=5))
+    need = lib.fva_demo_loss_workspace(5, levels, 2)
+    assert need > 0
+    assert getattr(lib, name)(p, 5, levels, 2, p, p, need, None) == -1
+    err = lib.fva_last_error().decode()
+    assert 'bad level shape' in err and err.startswith(name + ':'), err
+
+
 def test_ship_fit_loop_contract(tmp_path, monkeypatch):
     """warm-up ramp per iteration, min_lr on the validation loader in the no-augmentation phase, scheduler.step() only for
     warmup_epoch <= epoch < total_epoch - no_aug_epoch - 1, forward / zero_grad / three losses / backward / step, best-epoch_* and
