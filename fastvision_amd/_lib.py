@@ -228,12 +228,22 @@ PROTOTYPES = {
     'fva_bn_relu_frozen_bwd': (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     'fva_bn_frozen_bwd_finalize': (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P]),
     'fva_bn_frozen_stats': (_I, [_I, _P, _P, _P, _F, _P, _P, _P]),
+    'fva_stem7_kp': (_I, [_I, _I]),
+    'fva_stem7_patches': (_I, [_I, _P, _P, _I, _I, _I, _I, _P]),
+    'fva_maxpool3s2_fwd': (_I, [_I, _P, _I, _P, _I, _I, _I, _I, _I, _P]),
+    'fva_maxpool3s2_bwd': (_I, [_I, _P, _P, _I, _P, _I, _I, _I, _I, _P]),
+    'fva_subsample2_fwd': (_I, [_I, _P, _I, _P, _I, _I, _I, _I, _P]),
+    'fva_subsample2_bwd': (_I, [_I, _P, _P, _I, _I, _I, _I, _P]),
+    'fva_bn_add_relu_apply': (_I, [_I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    'fva_bn_add_relu_bwd_blocks': (_I, [_I, _L, _I]),
+    'fva_bn_add_relu_bwd_reduce': (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    'fva_bn_add_relu_bwd_apply': (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _P]),
 }
 LABEL_I64, LABEL_F32 = 0, 1
 REDUCE_MEAN, REDUCE_SUM = 0, 1
 UNCHECKED = {'fva_conv_patch_kernel', 'fva_sgd_chunk_elems', 'fva_ema_chunk_elems', 'fva_rows_relu_bwd_rows', 'fva_colour_workspace', 'fva_conv_dgrad_stat_rows', 'fva_bias_relu_bwd_rows', 'fva_colsum_scratch_rows', 'fva_last_error', 'fva_version', 'fva_profile_stop', 'fva_conv_last_kernel', 'fva_conv_packed_elems', 'fva_conv_stat_blocks', 'fva_conv_wgrad_workspace', 'fva_conv_wgrad_plan',
              'fva_stem_stat_blocks', 'fva_stem_fused_blocks', 'fva_stem_wgrad_workspace', 'fva_stem_fwd_workspace', 'fva_stem_wgrad_mfma_workspace', 'fva_bn_bwd_blocks', 'fva_bn_partial_rows', 'fva_yolov3_loss_workspace',
-             'fva_demo_loss_workspace', 'fva_demo_ciou_loss_workspace', 'fva_nms_candidates_workspace', 'fva_nms_select_workspace', 'fva_softmax_ce_workspace', 'fva_bn_frozen_bwd_blocks'}
+             'fva_demo_loss_workspace', 'fva_demo_ciou_loss_workspace', 'fva_nms_candidates_workspace', 'fva_nms_select_workspace', 'fva_softmax_ce_workspace', 'fva_bn_frozen_bwd_blocks', 'fva_stem7_kp', 'fva_bn_add_relu_bwd_blocks'}
 
 _lib = None
 

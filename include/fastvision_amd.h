@@ -758,6 +758,52 @@ int fva_adaptive_avgpool7_bwd(int dtype, const void* g, int B, int H, int W, int
 int fva_dropout_fwd(int dtype, const void* x, void* out, int64_t n, float p, int64_t* state, void* stream);
 int fva_dropout_bwd(int dtype, const void* dout, const void* out, void* dx, int64_t n, float p, void* stream);
 
+/* ---- ResNet classifiers (classfication/models/resnet.py; version 9) ---------------------------------------------------------------
+ * Streaming passes around the existing convolutions; dtype FVA_F32 / FVA_BF16, C a multiple of the 16-byte chunk (4 / 8 elements) up to
+ * 2048, borders 0 or 1, fixed summation order, no float atomics (run-to-run bit-identical).
+ *
+ * fva_stem7_patches: the 7x7 / stride 2 / pad 3 stem (resnet.py:136-140).  x: fp32 NCHW [B][Cin][H][W]; P: dense [B*OH*OW][Kp] of dtype,
+ *   OH = (H - 1) / 2 + 1, Kp = fva_stem7_kp(dtype, Cin) = Cin * 49 rounded up to a whole 128-byte k-tile of the implicit GEMM, 32 columns in
+ *   fp32 and 64 in bf16 (0 for a bad dtype or a Cin outside 1..1024); column ci * 49 + kh * 7 + kw
+ *   holds x[b][ci][2 oy - 3 + kh][2 ox - 3 + kw], taps outside the image and the columns from Cin * 49 on are zero.  The stem is then the
+ *   1x1 convolution over P (fva_conv_fwd / fva_conv_wgrad with ksize 1, Cin = Kp, H = OH, W = OW, in_pad 0); the first Cin * 49 columns
+ *   of its dW [Cout][Kp] are the weight gradient in OIHW order.
+ * fva_maxpool3s2_fwd / _bwd: nn.MaxPool2d(3, 2, 1) (resnet.py:142-144), any H, W >= 1, OH = (H - 1) / 2 + 1.  x: halo [B][H+2p][W+2p][C];
+ *   out: halo [B][OH+2q][OW+2q][C] with its zero border.  Taps outside the image count as -inf and are never read; a NaN in a window
+ *   makes the output NaN.  Backward (gather form, no argmax tensor): dz dense [B][OH][OW][C] -> dx dense [B][H][W][C]; a pixel takes dz
+ *   of the (at most four) windows in which torch's scan (kh, then kw ascending) ends on it -- the first maximum --, recomputed from x.
+ * fva_subsample2_fwd / _bwd: xs[b][i][j][c] = x[b][2i][2j][c] (resnet.py:49, :106: the stride of the 1x1 shortcut), H and W even.
+ *   x halo, xs dense [B][H/2][W/2][C].  Backward: dxs dense -> dx dense [B][H][W][C], dxs at the even positions and WRITTEN zeros
+ *   elsewhere (the `addend` of the main branch's fva_conv_dgrad).
+ * fva_bn_add_relu_*: z = max(0, u), u = y * scale + shift + R (resnet.py:64-71, :117-124), y dense [B*H*W][C].  Exactly one of
+ *   r      the identity: a halo tensor [B][H+2p][W+2p][C], p = r_pad; R = r                                       (form 1)
+ *   y_d    the dense output of the shortcut convolution, with scale_d / shift_d; R = y_d * scale_d + shift_d      (form 2)
+ *   is non-NULL.  u is recomputed in fp32 from the stored operands in all three passes (never read from the rounded z); a NaN stays a NaN.
+ *   _apply       z as a halo buffer [B][H+2q][W+2q][C] with its zero border, q = z_pad.  Eval mode: the coefficients of fva_bn_eval_coeffs.
+ *   _bwd_reduce  dU = dz * (u > 0), dz dense.  partial [fva_bn_add_relu_bwd_blocks()][2][C] = per-block sums of dU and dU * xhat; form 2
+ *                also partial_d [..][2][C] = sums of dU (the same numbers) and dU * xhat_d, xhat_d = (y_d - mean_d) * rstd_d.  Each table
+ *                goes through fva_bn_bwd_finalize as it is (allocate fva_bn_partial_rows(blocks) rows).
+ *   _bwd_apply   dy = a * dU + k1 * y + k2 from coef (fva_bn_bwd_finalize's [3][C] table), a halo buffer with zero border, p = dy_pad;
+ *                fp32 tensors form the sum in double.  Form 1 also writes dr = dU dense [B*H*W][C] (the identity's gradient); form 2 also
+ *                dy_d = a_d * dU + k1_d * y_d + k2_d from coef_d, a halo buffer like dy. */
+int32_t fva_stem7_kp(int dtype, int Cin);
+int fva_stem7_patches(int dtype, const float* x, void* P, int B, int Cin, int H, int W, void* stream);
+int fva_maxpool3s2_fwd(int dtype, const void* x, int x_pad, void* out, int out_pad, int B, int H, int W, int C, void* stream);
+int fva_maxpool3s2_bwd(int dtype, const void* dz, const void* x, int x_pad, void* dx, int B, int H, int W, int C, void* stream);
+int fva_subsample2_fwd(int dtype, const void* x, int x_pad, void* xs, int B, int H, int W, int C, void* stream);
+int fva_subsample2_bwd(int dtype, const void* dxs, void* dx, int B, int H, int W, int C, void* stream);
+int fva_bn_add_relu_apply(int dtype, const void* y, const float* scale, const float* shift, const void* r, int r_pad, const void* y_d,
+                          const float* scale_d, const float* shift_d, void* z, int z_pad, int B, int H, int W, int C, void* stream);
+int32_t fva_bn_add_relu_bwd_blocks(int dtype, int64_t M, int C);
+int fva_bn_add_relu_bwd_reduce(int dtype, const void* dz, const void* y, const float* scale, const float* shift, const float* save_mean,
+                               const float* save_rstd, const void* r, int r_pad, const void* y_d, const float* scale_d, const float* shift_d,
+                               const float* save_mean_d, const float* save_rstd_d, float* partial, float* partial_d, int32_t nblocks, int B, int H,
+                               int W, int C, void* stream);
+int fva_bn_add_relu_bwd_apply(int dtype, const void* dz, const void* y, const float* scale, const float* shift, const float* save_mean,
+                              const float* save_rstd, const float* coef, const void* r, int r_pad, const void* y_d, const float* scale_d,
+                              const float* shift_d, const float* save_mean_d, const float* save_rstd_d, const float* coef_d, void* dy, void* dy_d,
+                              int dy_pad, void* dr, int B, int H, int W, int C, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
