@@ -24,6 +24,11 @@ class ConvDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ('dtype', 'B', 'H', 'W', 'Cin', 'Cout', 'ksize', 'stride', 'in_pad', 'dy_pad')]
 
 
+class GConvDesc(C.Structure):
+    """fva_gconv_desc: the grouped 3x3 convolution (padding 1, Cin == Cout == C)"""
+    _fields_ = [(n, C.c_int32) for n in ('dtype', 'B', 'H', 'W', 'C', 'groups', 'stride', 'in_pad', 'dy_pad')]
+
+
 class HeadLevel(C.Structure):
     _fields_ = [('data', C.c_void_p), ('grad', C.c_void_p),
                 ('sb', C.c_int64), ('sa', C.c_int64), ('sy', C.c_int64), ('sx', C.c_int64), ('sk', C.c_int64),
@@ -102,6 +107,7 @@ class MatchOut(C.Structure):
 _P, _I, _L, _F = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 _D = C.POINTER(ConvDesc)
 _H = C.POINTER(HeadLevel)
+_G = C.POINTER(GConvDesc)
 
 # name -> (restype, argtypes); status-returning functions have restype int and are checked
 PROTOTYPES = {
@@ -238,12 +244,17 @@ PROTOTYPES = {
     'fva_bn_add_relu_bwd_blocks': (_I, [_I, _L, _I]),
     'fva_bn_add_relu_bwd_reduce': (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     'fva_bn_add_relu_bwd_apply': (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _P]),
+    'fva_gconv_fwd': (_I, [_G, _P, _P, _P, _P, _P]),
+    'fva_gconv_stat_blocks': (_I, [_G]),
+    'fva_gconv_dgrad': (_I, [_G, _P, _P, _P, _P]),
+    'fva_gconv_wgrad': (_I, [_G, _P, _P, _P, _P, _L, _P]),
+    'fva_gconv_wgrad_workspace': (_L, [_G]),
 }
 LABEL_I64, LABEL_F32 = 0, 1
 REDUCE_MEAN, REDUCE_SUM = 0, 1
 UNCHECKED = {'fva_conv_patch_kernel', 'fva_sgd_chunk_elems', 'fva_ema_chunk_elems', 'fva_rows_relu_bwd_rows', 'fva_colour_workspace', 'fva_conv_dgrad_stat_rows', 'fva_bias_relu_bwd_rows', 'fva_colsum_scratch_rows', 'fva_last_error', 'fva_version', 'fva_profile_stop', 'fva_conv_last_kernel', 'fva_conv_packed_elems', 'fva_conv_stat_blocks', 'fva_conv_wgrad_workspace', 'fva_conv_wgrad_plan',
              'fva_stem_stat_blocks', 'fva_stem_fused_blocks', 'fva_stem_wgrad_workspace', 'fva_stem_fwd_workspace', 'fva_stem_wgrad_mfma_workspace', 'fva_bn_bwd_blocks', 'fva_bn_partial_rows', 'fva_yolov3_loss_workspace',
-             'fva_demo_loss_workspace', 'fva_demo_ciou_loss_workspace', 'fva_nms_candidates_workspace', 'fva_nms_select_workspace', 'fva_softmax_ce_workspace', 'fva_bn_frozen_bwd_blocks', 'fva_stem7_kp', 'fva_bn_add_relu_bwd_blocks'}
+             'fva_demo_loss_workspace', 'fva_demo_ciou_loss_workspace', 'fva_nms_candidates_workspace', 'fva_nms_select_workspace', 'fva_softmax_ce_workspace', 'fva_bn_frozen_bwd_blocks', 'fva_stem7_kp', 'fva_bn_add_relu_bwd_blocks', 'fva_gconv_stat_blocks', 'fva_gconv_wgrad_workspace'}
 
 _lib = None
 

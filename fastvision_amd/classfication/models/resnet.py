@@ -15,7 +15,8 @@ The ``nn`` modules only own parameters and settings; ``forward`` runs
     AdaptiveAvgPool2d(1) + flatten     ops.global_avg_pool
     Linear                             fc_ops.linear                  (fp32 logits [B, num_classes])
 
-Constructing a model needs no GPU; ``forward`` on CPU tensors raises.  ResNeXt (grouped convolutions) is not built.
+Constructing a model needs no GPU; ``forward`` on CPU tensors raises.  ResNeXt lives in resnext.py: this chain with a
+grouped conv2 (csrc/grouped.hip).
 """
 import torch.nn as nn
 

@@ -804,6 +804,27 @@ int fva_bn_add_relu_bwd_apply(int dtype, const void* dz, const void* y, const fl
                               const float* shift_d, const float* save_mean_d, const float* save_rstd_d, const float* coef_d, void* dy, void* dy_d,
                               int dy_pad, void* dr, int B, int H, int W, int C, void* stream);
 
+/* ---- Grouped 3x3 convolution (classfication/models/resnext.py:40, conv2 of the ResNeXt bottleneck; version 10) ------------------------
+ * 3x3, padding 1, stride 1 or 2, Cin == Cout == C, bias-free.  Contract: C = groups * Cg with Cg in {4, 8, 16, 32, 64}, C % 64 == 0,
+ * C <= 2048; stride 2 needs even H and W; dtype FVA_F32 / FVA_BF16; in_pad and dy_pad in 1 ... 8.  Anything else returns FVA_ERR_ARG with a
+ * message (fva_last_error) and launches nothing.  OH = (H - 1) / stride + 1.
+ *   x   halo NHWC [B][H + 2 in_pad][W + 2 in_pad][C] (zero border)       y    dense [B*OH*OW][C]
+ *   dy  halo NHWC [B][OH + 2 dy_pad][OW + 2 dy_pad][C] (zero border: what fva_bn_relu_bwd_apply writes)
+ *   dx  dense [B][H][W][C]                                               dw   fp32 [C][Cg][3][3], the parameter's own shape
+ *   w_oihw: the fp32 master weight [C][Cg][3][3] as it stands; bf16 tensors multiply its bf16 rounding.  No packed copy exists and
+ *   nothing is cached between calls.
+ *   stats_partial: [fva_bn_partial_rows(fva_gconv_stat_blocks(d))][2][C], per block of 256 output pixels the sums of y and y^2 (of the
+ *   unrounded accumulators, in pixel order); fva_bn_finalize takes it unchanged.  NULL: no statistics (eval mode).
+ *   fva_gconv_wgrad: workspace of fva_gconv_wgrad_workspace(d) bytes (0 for a descriptor outside the contract); FVA_ERR_WORKSPACE if short.
+ * No float atomics, fixed summation order: every launch gives the same bits twice.  fp32 tensors accumulate in double and round once.
+ * All three run on plain FMA kernels at both strides (grouped.hip); no MFMA kernel is built. */
+typedef struct { int32_t dtype, B, H, W, C, groups, stride, in_pad, dy_pad; } fva_gconv_desc;   /* 3x3, padding 1, Cin == Cout == C */
+int     fva_gconv_fwd(const fva_gconv_desc*, const void* x, const float* w_oihw, void* y, float* stats_partial, void* stream);
+int32_t fva_gconv_stat_blocks(const fva_gconv_desc*);
+int     fva_gconv_dgrad(const fva_gconv_desc*, const void* dy, const float* w_oihw, void* dx, void* stream);
+int     fva_gconv_wgrad(const fva_gconv_desc*, const void* x, const void* dy, float* dw_oihw, void* workspace, int64_t workspace_bytes, void* stream);
+int64_t fva_gconv_wgrad_workspace(const fva_gconv_desc*);
+
 #ifdef __cplusplus
 }
 #endif
