@@ -4,9 +4,9 @@
                                      patch matrix, fva_bn_finalize, fva_bn_relu_apply; backward = the BatchNorm + ReLU passes, then fva_conv_wgrad
                                      over the same patch matrix (the images get no gradient)
     max_pool3s2(x)                   MaxPool2d(3, 2, 1); backward recomputes the first maximum from x
-    conv_bn_relu(x, conv, bn)        bias-free Conv2d (1x1 s1, 3x3 s1, 3x3 s2) -> BatchNorm2d -> ReLU: the C calls of vgg_ops.ConvBNReLUFn
-                                     without the bias bookkeeping; frozen statistics take the one-pass backward (ops.frozen_bn_bwd).
-                                     A grouped 3x3 (ResNeXt's conv2; GROUPED_CONTRACT) runs fva_gconv_fwd / _dgrad / _wgrad instead
+    conv_bn_relu(x, conv, bn)        bias-free Conv2d (1x1 s1, 3x3 s1, 3x3 s2) -> BatchNorm2d -> ReLU: conv_bn_ops.ConvBNReLUFn, the node that
+                                     vgg_ops.conv_bn_relu runs too, without a bias; frozen statistics take the one-pass backward.  A grouped
+                                     3x3 (ResNeXt's conv2; GROUPED_CONTRACT) is the same node on conv_bn_ops.GroupedConv (fva_gconv_*)
     conv_bn_add_relu(x, conv, bn, identity)
     conv_bn_add_relu(x, conv, bn, shortcut_in, shortcut_conv, shortcut_bn)
                                      the tail of a residual block, relu(bn(conv(x)) + R) with the add INSIDE the ReLU, one autograd node:
@@ -20,14 +20,19 @@ Any other wiring gets the summand back through autograd as usual.
 
 Activations stay in the halo NHWC layout between blocks, in the compute dtype; parameters and their gradients are fp32; running
 statistics and num_batches_tracked are updated on the device; nothing synchronises the host.  No CPU path.
+
+The conv -> BatchNorm -> ReLU node, the max-pool node and the BatchNorm + ReLU pieces that the stem and the tail use are conv_bn_ops';
+this module keeps the public functions, their argument checks, the stem, the tail and the ``_Link``.
 """
 import ctypes as C
 
 import torch
 
 from . import _lib
-from .ops import (_BNState, _code, _grad_like, _p, _released, _stream, _wgrad_dgrad, flush_pending_apply, frozen_bn_bwd, get_compute_dtype,
-                  halo_alloc, packed_weights, require_gpu, to_dense, to_halo, wgrad_stream)
+from .conv_bn_ops import (WIDE_FROZEN, ConvBNReLUFn, GroupedConv, MaxPoolFn, PlainConv, _block_bn_relu_bwd, _bn_add_relu_bwd_identity, _check_bn,  # noqa: F401
+                          _conv_bn, _wide)
+from .ops import (_BNState, _code, _grad_like, _p, _released, _stream, _wgrad_dgrad, flush_pending_apply, get_compute_dtype, halo_alloc,
+                  packed_weights, require_gpu, to_dense, to_halo)
 
 __all__ = ['stem_bn_relu', 'max_pool3s2', 'conv_bn_relu', 'conv_bn_add_relu']
 
@@ -42,97 +47,6 @@ class _Link:
     def __init__(self):
         self.shape = self.dtype = self.x_ptr = self.addend = None
         self.open = self.taken = False
-
-
-def _check_bn(bn, who):
-    if not bn.affine:
-        raise RuntimeError(f'{who}: the BatchNorm2d must be affine')
-    if bn.training and bn.momentum is None and bn.track_running_stats:
-        raise RuntimeError(f'{who}: momentum=None (cumulative average) is not on this path')
-    return bn.training or not bn.track_running_stats
-
-
-def _conv_bn(d, x_ptr, wf, gamma, beta, bn, training, M, dev, dtype, who, fwd='fva_conv_fwd', blocks='fva_conv_stat_blocks'):
-    """The convolution with (training) or without batch statistics and the BatchNorm coefficients: (y, scale, shift, mean, rstd).
-    ``fwd`` / ``blocks``: the forward launch and its statistics-block count (the grouped 3x3: fva_gconv_fwd / fva_gconv_stat_blocks on a
-    GConvDesc and the fp32 master weight)."""
-    lib = _lib.load()
-    Cout = d.C if isinstance(d, _lib.GConvDesc) else d.Cout
-    y = torch.empty((M, Cout), dtype=dtype, device=dev)
-    scale = torch.empty(Cout, dtype=torch.float32, device=dev)
-    shift = torch.empty_like(scale)
-    mean = rstd = None
-    if training:
-        nblk = getattr(lib, blocks)(C.byref(d))
-        stats = torch.empty((lib.fva_bn_partial_rows(nblk), 2, Cout), dtype=torch.float32, device=dev)
-        mean, rstd = torch.empty_like(scale), torch.empty_like(scale)
-        _lib.call(fwd, C.byref(d), C.c_void_p(x_ptr), _p(wf), _p(y), _p(stats), _stream())
-        _lib.call('fva_bn_finalize', _p(stats), nblk, stats.shape[0], M, Cout, _p(gamma), _p(beta), _p(bn.rm), _p(bn.rv), _p(bn.nbt),
-                  bn.momentum, bn.eps, _p(mean), _p(rstd), _p(scale), _p(shift), _stream())
-    else:
-        if bn.rm is None:
-            raise RuntimeError(f'{who}: eval mode needs running statistics (track_running_stats=True)')
-        _lib.call(fwd, C.byref(d), C.c_void_p(x_ptr), _p(wf), _p(y), C.c_void_p(0), _stream())
-        _lib.call('fva_bn_eval_coeffs', Cout, _p(gamma), _p(beta), _p(bn.rm), _p(bn.rv), bn.eps, _p(scale), _p(shift), _stream())
-    return y, scale, shift, mean, rstd
-
-
-def _wide(code, Cout):
-    """fva_bn_relu_* serve at most 256 16-byte chunks per pixel: 2048 channels in bf16, 1024 in fp32.  Wider fp32 tensors (the 2048
-    channels of resnext101_32x8d's res5, in the fp32 parity runs) take the BatchNorm + add + ReLU passes with a zero addend instead."""
-    return Cout // (8 if code == _lib.BF16 else 4) > 256
-
-
-WIDE_FROZEN = ('conv_bn_relu: backward with frozen statistics (the BatchNorm in eval mode) through an fp32 tensor wider than 1024 channels is not '
-               'on this path -- the one-pass frozen backward serves at most 256 16-byte chunks per pixel; run it in bf16, or keep the BatchNorm in '
-               'training mode')
-
-
-def _bn_relu_apply(code, y, scale, shift, zbuf, B, H, W, Cout):
-    """z = relu(y * scale + shift) into the halo buffer zbuf (border 1)."""
-    if not _wide(code, Cout):
-        _lib.call('fva_bn_relu_apply', code, _p(y), _p(scale), _p(shift), _p(zbuf), 1, B, H, W, Cout, _stream())
-        return
-    none = C.c_void_p(0)
-    r = torch.zeros((B, H, W, Cout), dtype=y.dtype, device=y.device)
-    _lib.call('fva_bn_add_relu_apply', code, _p(y), _p(scale), _p(shift), _p(r), 0, none, none, none, _p(zbuf), 1, B, H, W, Cout, _stream())
-
-
-def _bn_relu_bwd_wide(code, dz_ptr, y, scale, shift, mean, rstd, gamma, B, H, W, Cout, dtype):
-    """_bn_relu_bwd through the add + ReLU passes (identity form) with a zero addend; the addend's gradient is dropped."""
-    lib, dev, M = _lib.load(), y.device, B * H * W
-    f32 = dict(dtype=torch.float32, device=dev)
-    r = torch.zeros((B, H, W, Cout), dtype=dtype, device=dev)
-    nb = lib.fva_bn_add_relu_bwd_blocks(code, M, Cout)
-    rows = lib.fva_bn_partial_rows(nb)
-    part = torch.empty((rows, 2, Cout), **f32)
-    dgamma, dbeta, coef = torch.empty(Cout, **f32), torch.empty(Cout, **f32), torch.empty((3, Cout), **f32)
-    dy = torch.empty((B, H + 2, W + 2, Cout), dtype=dtype, device=dev)
-    dr = torch.empty((B, H, W, Cout), dtype=dtype, device=dev)
-    main = (code, C.c_void_p(dz_ptr), _p(y), _p(scale), _p(shift), _p(mean), _p(rstd))
-    _lib.call('fva_bn_add_relu_bwd_reduce', *main, _p(r), 0, None, None, None, None, None, _p(part), None, nb, B, H, W, Cout, _stream())
-    _lib.call('fva_bn_bwd_finalize', _p(part), nb, rows, M, Cout, _p(gamma), _p(rstd), _p(dgamma), _p(dbeta), 0, _p(coef), _stream())
-    _lib.call('fva_bn_add_relu_bwd_apply', *main, _p(coef), _p(r), 0, None, None, None, None, None, None, _p(dy), None, 1, _p(dr), B, H, W, Cout,
-              _stream())
-    return dy, dgamma, dbeta
-
-
-def _bn_relu_bwd(code, dz_ptr, y, scale, shift, mean, rstd, gamma, B, H, W, Cout, dtype):
-    """The two BatchNorm + ReLU backward passes (training mode): (dy halo, dgamma, dbeta)."""
-    if _wide(code, Cout):
-        return _bn_relu_bwd_wide(code, dz_ptr, y, scale, shift, mean, rstd, gamma, B, H, W, Cout, dtype)
-    lib, dev, M = _lib.load(), y.device, B * H * W
-    nb = lib.fva_bn_bwd_blocks(code, M, Cout)
-    part = torch.empty((lib.fva_bn_partial_rows(nb), 2, Cout), dtype=torch.float32, device=dev)
-    _lib.call('fva_bn_relu_bwd_reduce', code, C.c_void_p(dz_ptr), _p(y), _p(scale), _p(shift), _p(mean), _p(rstd), _p(part), nb, M, Cout, _stream())
-    dgamma = torch.empty(Cout, dtype=torch.float32, device=dev)
-    dbeta = torch.empty_like(dgamma)
-    coef = torch.empty((3, Cout), dtype=torch.float32, device=dev)
-    _lib.call('fva_bn_bwd_finalize', _p(part), nb, part.shape[0], M, Cout, _p(gamma), _p(rstd), _p(dgamma), _p(dbeta), 0, _p(coef), _stream())
-    dy = torch.empty((B, H + 2, W + 2, Cout), dtype=dtype, device=dev)
-    _lib.call('fva_bn_relu_bwd_apply', code, C.c_void_p(dz_ptr), _p(y), _p(scale), _p(shift), _p(mean), _p(rstd), _p(coef), _p(dy), 1,
-              B, H, W, Cout, _stream())
-    return dy, dgamma, dbeta
 
 
 # ------------------------------------------------------------------------------------------------ the stem
@@ -174,12 +88,9 @@ class StemBNReLUFn(torch.autograd.Function):
         B, OH, OW, Cout, Kp, dev, code = d.B, d.H, d.W, d.Cout, d.Cin, y.device, _code(dtype)
         keep_dz, dz_ptr = to_dense(dz, dtype)
         need_w, need_g, need_b = ctx.needs_input_grad[1:4]
-        if ctx.training:
-            dy, dgamma, dbeta = _bn_relu_bwd(code, dz_ptr, y, scale, shift, mean, rstd, gamma, B, OH, OW, Cout, dtype)
-        else:
-            dy = torch.empty((B, OH + 2, OW + 2, Cout), dtype=dtype, device=dev)
-            dgamma, dbeta, _ = frozen_bn_bwd('relu', code, dz_ptr, y, scale, shift, ctx.bn, None, dy, 1, B, OH, OW, Cout, need_g, need_b)
-            ctx.bn = None
+        dy, dgamma, dbeta, _ = _block_bn_relu_bwd(ctx.training, code, dz_ptr, y, scale, shift, mean, rstd, gamma, ctx.bn, None, B, OH, OW, Cout,
+                                                  dtype, need_g, need_b)
+        ctx.bn = None
         dw = None
         if need_w or ctx.training:
             # on the launch stream: the slice below reads dW right away
@@ -203,31 +114,9 @@ def stem_bn_relu(x, conv, bn, dtype=None):
 
 
 # ------------------------------------------------------------------------------------------------ MaxPool2d(3, 2, 1)
-class MaxPool3s2Fn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, dtype):
-        require_gpu(x, 'max_pool3s2')
-        flush_pending_apply()
-        B, Cc, H, W = x.shape
-        keep, x_ptr, x_pad = to_halo(x.detach(), dtype, 0)
-        obuf, out = halo_alloc(B, Cc, (H - 1) // 2 + 1, (W - 1) // 2 + 1, dtype, x.device, 1)
-        _lib.call('fva_maxpool3s2_fwd', _code(dtype), C.c_void_p(x_ptr), x_pad, _p(obuf), 1, B, H, W, Cc, _stream())
-        ctx.saved = (keep, x_ptr, x_pad, (B, Cc, H, W), dtype)
-        ctx.x_like = x
-        return out
-
-    @staticmethod
-    def backward(ctx, dz):
-        keep, x_ptr, x_pad, (B, Cc, H, W), dtype = ctx.saved
-        keep_dz, dz_ptr = to_dense(dz, dtype)
-        dxb = torch.empty((B, H, W, Cc), dtype=dtype, device=dz.device)
-        _lib.call('fva_maxpool3s2_bwd', _code(dtype), C.c_void_p(dz_ptr), C.c_void_p(x_ptr), x_pad, _p(dxb), B, H, W, Cc, _stream())
-        return _grad_like(dxb, ctx.x_like), None
-
-
 def max_pool3s2(x, dtype=None):
     """``nn.MaxPool2d(kernel_size=3, stride=2, padding=1)``"""
-    return MaxPool3s2Fn.apply(x, dtype or get_compute_dtype())
+    return MaxPoolFn.apply(x, dtype or get_compute_dtype(), 'max_pool3s2', 'fva_maxpool3s2_fwd', 'fva_maxpool3s2_bwd', lambda n: (n - 1) // 2 + 1)
 
 
 # ------------------------------------------------------------------------------------------------ conv -> BN -> ReLU
@@ -244,124 +133,14 @@ def _even_map(x, stride, who):
         raise RuntimeError(f'{who}: a stride-2 block needs an even map, got {x.shape[2]} x {x.shape[3]} (odd map in front of a stride-2 block)')
 
 
-class ConvBNReLUFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, weight, gamma, beta, bn, training, dtype, k, stride, link):
-        require_gpu(x, 'conv_bn_relu')
-        flush_pending_apply()
-        B, Cin, H, W = x.shape
-        Cout, dev, code = weight.shape[0], x.device, _code(dtype)
-        keep, x_ptr, x_pad = to_halo(x.detach(), dtype, k // 2)
-        d = _lib.ConvDesc(code, B, H, W, Cin, Cout, k, stride, x_pad, 1)
-        wf, wd = packed_weights(weight, d, dtype, cache=weight.is_leaf)
-        OH, OW = (H - 1) // stride + 1, (W - 1) // stride + 1
-        y, scale, shift, mean, rstd = _conv_bn(d, x_ptr, wf, gamma, beta, bn, training, B * OH * OW, dev, dtype, 'conv_bn_relu')
-        zbuf, z = halo_alloc(B, Cout, OH, OW, dtype, dev, 1)
-        _bn_relu_apply(code, y, scale, shift, zbuf, B, OH, OW, Cout)
-        need = link is not None and any(ctx.needs_input_grad)
-        ctx.saved = (keep, x_ptr, y, scale, shift, mean, rstd, d, wd, dtype, tuple(weight.shape), gamma, OH, OW) if need else None
-        ctx.training, ctx.bn = training, (None if training else bn)
-        ctx.x_like, ctx.weight, ctx.link = x, weight, link
-        if need:
-            link.shape, link.dtype, link.x_ptr, link.open = tuple(x.shape), dtype, x_ptr, True
-        return z
-
-    @staticmethod
-    def backward(ctx, dz):
-        if ctx.saved is None:
-            raise _released('conv_bn_relu')
-        keep, x_ptr, y, scale, shift, mean, rstd, d, wd, dtype, wshape, gamma, OH, OW = ctx.saved
-        B, Cout, dev, code = d.B, d.Cout, y.device, _code(dtype)
-        link = ctx.link
-        link.open = False                                       # a tail that runs its backward later keeps its summand for autograd
-        addend, link.addend = link.addend, None
-        keep_dz, dz_ptr = to_dense(dz, dtype)
-        need_x, need_w, need_g, need_b = ctx.needs_input_grad[:4]
-        if ctx.training:
-            need_w = True
-            dy, dgamma, dbeta = _bn_relu_bwd(code, dz_ptr, y, scale, shift, mean, rstd, gamma, B, OH, OW, Cout, dtype)
-        else:
-            # frozen statistics: one pass, and only what autograd asks for
-            if _wide(code, Cout):
-                raise RuntimeError(WIDE_FROZEN)
-            dy = torch.empty((B, OH + 2, OW + 2, Cout), dtype=dtype, device=dev)
-            dgamma, dbeta, _ = frozen_bn_bwd('relu', code, dz_ptr, y, scale, shift, ctx.bn, None, dy, 1, B, OH, OW, Cout, need_g, need_b)
-        dxb, dw = _wgrad_dgrad(d, x_ptr, dy, wd, wshape, (keep,), ctx.weight, need_x, addend_ptr=None if addend is None else addend.data_ptr(),
-                               need_dw=need_w)
-        dx = _grad_like(dxb, ctx.x_like) if dxb is not None else None
-        ctx.saved = ctx.x_like = ctx.weight = ctx.bn = ctx.link = None          # released by the backward pass that used them
-        return dx, dw, dgamma, dbeta, None, None, None, None, None, None
-
-
 GROUPED_CONTRACT = ('conv_bn_relu: a grouped convolution is on this path as a 3x3 of stride 1 or 2 with in_channels == out_channels == C, '
                     'C = groups * Cg, Cg in {4, 8, 16, 32, 64}, C % 64 == 0 and C <= 2048')
 
 
-class GroupedConvBNReLUFn(torch.autograd.Function):
-    """conv_bn_relu for ``groups > 1``: the three convolution calls go to fva_gconv_fwd / _dgrad / _wgrad on the fp32 master weight (no packed
-    copy, nothing registered with ops._PackRegistry); everything around them is ConvBNReLUFn's.  The node keeps no link to a block's tail:
-    its data gradient takes no addend, the tail's summand comes back through autograd."""
-
-    @staticmethod
-    def forward(ctx, x, weight, gamma, beta, bn, training, dtype, groups, stride, grad_on):
-        require_gpu(x, 'conv_bn_relu')
-        flush_pending_apply()
-        B, Cc, H, W = x.shape
-        dev, code = x.device, _code(dtype)
-        keep, x_ptr, x_pad = to_halo(x.detach(), dtype, 1)
-        d = _lib.GConvDesc(code, B, H, W, Cc, groups, stride, x_pad, 1)
-        w = weight.detach()
-        if w.dtype != torch.float32 or not w.is_contiguous():
-            w = w.float().contiguous()
-        OH, OW = (H - 1) // stride + 1, (W - 1) // stride + 1
-        y, scale, shift, mean, rstd = _conv_bn(d, x_ptr, w, gamma, beta, bn, training, B * OH * OW, dev, dtype, 'conv_bn_relu', 'fva_gconv_fwd',
-                                               'fva_gconv_stat_blocks')
-        zbuf, z = halo_alloc(B, Cc, OH, OW, dtype, dev, 1)
-        _bn_relu_apply(code, y, scale, shift, zbuf, B, OH, OW, Cc)
-        need = grad_on and any(ctx.needs_input_grad)
-        ctx.saved = (keep, x_ptr, y, scale, shift, mean, rstd, d, w, dtype, tuple(weight.shape), gamma, OH, OW) if need else None
-        ctx.training, ctx.bn = training, (None if training else bn)
-        ctx.x_like, ctx.weight = x, weight
-        return z
-
-    @staticmethod
-    def backward(ctx, dz):
-        if ctx.saved is None:
-            raise _released('conv_bn_relu')
-        keep, x_ptr, y, scale, shift, mean, rstd, d, w, dtype, wshape, gamma, OH, OW = ctx.saved
-        lib = _lib.load()
-        B, Cc, dev, code = d.B, d.C, y.device, _code(dtype)
-        keep_dz, dz_ptr = to_dense(dz, dtype)
-        need_x, need_w, need_g, need_b = ctx.needs_input_grad[:4]
-        if ctx.training:
-            need_w = True
-            dy, dgamma, dbeta = _bn_relu_bwd(code, dz_ptr, y, scale, shift, mean, rstd, gamma, B, OH, OW, Cc, dtype)
-        else:
-            if _wide(code, Cc):
-                raise RuntimeError(WIDE_FROZEN)
-            dy = torch.empty((B, OH + 2, OW + 2, Cc), dtype=dtype, device=dev)
-            dgamma, dbeta, _ = frozen_bn_bwd('relu', code, dz_ptr, y, scale, shift, ctx.bn, None, dy, 1, B, OH, OW, Cc, need_g, need_b)
-        dw = dx = None
-        if need_w:
-            dw = torch.empty(wshape, dtype=torch.float32, device=dev)
-            wsb = lib.fva_gconv_wgrad_workspace(C.byref(d))
-            ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-            _lib.call('fva_gconv_wgrad', C.byref(d), C.c_void_p(x_ptr), _p(dy), _p(dw), _p(ws), wsb, wgrad_stream((keep, dy, ws), ctx.weight))
-        if need_x:
-            dxb = torch.empty((B, d.H, d.W, Cc), dtype=dtype, device=dev)
-            _lib.call('fva_gconv_dgrad', C.byref(d), _p(dy), _p(w), _p(dxb), _stream())
-            dx = _grad_like(dxb, ctx.x_like)
-        ctx.saved = ctx.x_like = ctx.weight = ctx.bn = None
-        return dx, dw, dgamma, dbeta, None, None, None, None, None, None
-
-
-def _grouped_conv_bn_relu(x, conv, bn, stride, dtype):
+def _check_grouped(x, conv):
     Cc, groups = conv.in_channels, conv.groups
     if conv.out_channels != Cc or Cc % groups or Cc // groups not in (4, 8, 16, 32, 64) or Cc % 64 or Cc > 2048 or x.shape[1] != Cc:
         raise RuntimeError(f'{GROUPED_CONTRACT}; got {conv} on an input of {x.shape[1]} channels')
-    training = _check_bn(bn, 'conv_bn_relu')
-    return GroupedConvBNReLUFn.apply(x, conv.weight, bn.weight, bn.bias, _BNState(bn), training, dtype or get_compute_dtype(), groups, stride,
-                                     torch.is_grad_enabled())
 
 
 def conv_bn_relu(x, conv, bn, dtype=None):
@@ -369,11 +148,13 @@ def conv_bn_relu(x, conv, bn, dtype=None):
     ``nn.BatchNorm2d``; the module's ``training`` flag, momentum and eps are read at call time.  The 3x3 may be grouped (GROUPED_CONTRACT)."""
     k, stride = _conv_geometry(conv, 'conv_bn_relu', {(1, 1), (3, 1), (3, 2)}, grouped=True)
     _even_map(x, stride, 'conv_bn_relu')
-    if conv.groups != 1:
-        return _grouped_conv_bn_relu(x, conv, bn, stride, dtype)
+    grouped, grad_on = conv.groups != 1, torch.is_grad_enabled()
+    if grouped:
+        _check_grouped(x, conv)
     training = _check_bn(bn, 'conv_bn_relu')
-    link = _Link() if torch.is_grad_enabled() else None
-    z = ConvBNReLUFn.apply(x, conv.weight, bn.weight, bn.bias, _BNState(bn), training, dtype or get_compute_dtype(), k, stride, link)
+    back_end = GroupedConv(conv.groups, stride) if grouped else PlainConv(k, stride)
+    link = _Link() if grad_on and not grouped else None         # the grouped data gradient takes no addend: no link to the block's tail
+    z = ConvBNReLUFn.apply(x, conv.weight, None, bn.weight, bn.bias, _BNState(bn), training, dtype or get_compute_dtype(), back_end, link, grad_on)
     if link is not None and link.open:
         x._fva_block_in = link                                  # a tail whose second operand is this very tensor finds the node here
     return z
@@ -436,24 +217,20 @@ class ConvBNAddReLUFn(torch.autograd.Function):
         B, H, W, Cout, dev, code = d.B, d.H, d.W, d.Cout, y.device, _code(dtype)
         M = B * H * W
         keep_dz, dz_ptr = to_dense(dz, dtype)
-        f32 = dict(dtype=torch.float32, device=dev)
-        nb = lib.fva_bn_add_relu_bwd_blocks(code, M, Cout)
-        rows = lib.fva_bn_partial_rows(nb)
-        part = torch.empty((rows, 2, Cout), **f32)
-        dgamma, dbeta, coef = torch.empty(Cout, **f32), torch.empty(Cout, **f32), torch.empty((3, Cout), **f32)
-        dy = torch.empty((B, H + 2, W + 2, Cout), dtype=dtype, device=dev)
-        main = (code, C.c_void_p(dz_ptr), _p(y), _p(scale), _p(shift), _p(mean), _p(rstd))
         if short is None:
-            _lib.call('fva_bn_add_relu_bwd_reduce', *main, C.c_void_p(o_ptr), o_pad, None, None, None, None, None, _p(part), None, nb, B, H, W, Cout,
-                      _stream())
-            _lib.call('fva_bn_bwd_finalize', _p(part), nb, rows, M, Cout, _p(gamma), _p(rstd), _p(dgamma), _p(dbeta), 0, _p(coef), _stream())
-            other_grad = torch.empty((B, H, W, Cout), dtype=dtype, device=dev)          # dr = dU: the identity's gradient
-            _lib.call('fva_bn_add_relu_bwd_apply', *main, _p(coef), C.c_void_p(o_ptr), o_pad, None, None, None, None, None, None, _p(dy), None, 1,
-                      _p(other_grad), B, H, W, Cout, _stream())
+            # dr = dU: the identity's gradient
+            dy, other_grad, dgamma, dbeta = _bn_add_relu_bwd_identity(code, dz_ptr, y, scale, shift, mean, rstd, gamma, o_ptr, o_pad, B, H, W, Cout,
+                                                                      dtype)
             dw_d = dgamma_d = dbeta_d = None
         else:
             dd, wd_d, y_d, scale_d, shift_d, mean_d, rstd_d, wshape_d, gamma_d, (Hs, Ws, Cd) = short
-            part_d = torch.empty((rows, 2, Cout), **f32)
+            f32 = dict(dtype=torch.float32, device=dev)
+            nb = lib.fva_bn_add_relu_bwd_blocks(code, M, Cout)
+            rows = lib.fva_bn_partial_rows(nb)
+            part, part_d = torch.empty((rows, 2, Cout), **f32), torch.empty((rows, 2, Cout), **f32)
+            dgamma, dbeta, coef = torch.empty(Cout, **f32), torch.empty(Cout, **f32), torch.empty((3, Cout), **f32)
+            dy = torch.empty((B, H + 2, W + 2, Cout), dtype=dtype, device=dev)
+            main = (code, C.c_void_p(dz_ptr), _p(y), _p(scale), _p(shift), _p(mean), _p(rstd))
             sc = (_p(y_d), _p(scale_d), _p(shift_d), _p(mean_d), _p(rstd_d))
             _lib.call('fva_bn_add_relu_bwd_reduce', *main, None, 0, *sc, _p(part), _p(part_d), nb, B, H, W, Cout, _stream())
             dgamma_d, dbeta_d, coef_d = torch.empty(Cout, **f32), torch.empty(Cout, **f32), torch.empty((3, Cout), **f32)

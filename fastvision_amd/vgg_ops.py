@@ -3,10 +3,10 @@ VGG16 (demos/faster_rcnn/models/vgg.py) -- ``nn.Conv2d(3x3, padding 1, bias) -> 
 
     conv_bias_relu(x, conv)      one Conv2d + ReLU block: implicit-GEMM conv with the bias + ReLU epilogue; backward = ReLU mask
                                  and bias gradient in one pass, then the library's dgrad / wgrad (wgrad on the side stream)
-    max_pool2(x)                 MaxPool2d(2, 2)
+    max_pool2(x)                 MaxPool2d(2, 2): conv_bn_ops.MaxPoolFn
     conv_bn_relu(x, conv, bn)    Conv2d(bias) -> BatchNorm2d -> ReLU of the classifiers' ``_bn`` variants (classfication/models/vgg.py:39-48):
-                                 conv with batch statistics, fva_bn_finalize, fva_bn_relu_apply; backward = the two BatchNorm + ReLU passes
-                                 (fva_bn_relu_bwd_reduce / fva_bn_bwd_finalize / fva_bn_relu_bwd_apply), then dgrad / wgrad
+                                 conv_bn_ops.ConvBNReLUFn, the node that resnet_ops.conv_bn_relu runs too, here with the convolution bias
+                                 (its docstring says where the bias goes); this module keeps the argument checks and the RGB padding
     adaptive_avg_pool7_flatten(x)  AdaptiveAvgPool2d((7, 7)) + flatten -> [B, C*49] in the compute dtype (the first Linear's operand)
 
 Activations stay in the package's halo NHWC layout between blocks (the returned tensors are [B,C,H,W] views of it), in the
@@ -18,9 +18,10 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib
+from .conv_bn_ops import ConvBNReLUFn, MaxPoolFn, PlainConv, _check_bn
 from .fc_ops import rows_as
-from .ops import (_BNState, _code, _grad_like, _p, _released, _stream, _wgrad_dgrad, dense_view, flush_pending_apply, frozen_bn_bwd, get_compute_dtype,
-                  halo_alloc, halo_info, packed_weights, require_gpu, to_dense, to_halo)
+from .ops import (_BNState, _code, _grad_like, _p, _stream, _wgrad_dgrad, dense_view, flush_pending_apply, get_compute_dtype, halo_alloc,
+                  packed_weights, require_gpu, to_dense, to_halo)
 
 __all__ = ['conv_bias_relu', 'max_pool2', 'conv_bn_relu', 'adaptive_avg_pool7_flatten']
 
@@ -62,27 +63,6 @@ class ConvBiasReLUFn(torch.autograd.Function):
         return dx, dw, dbias, None
 
 
-class MaxPool2Fn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, dtype):
-        require_gpu(x, 'max_pool2')
-        B, Cc, H, W = x.shape
-        keep, x_ptr, x_pad = to_halo(x.detach(), dtype, 0)
-        obuf, out = halo_alloc(B, Cc, H // 2, W // 2, dtype, x.device, 1)
-        _lib.call('fva_maxpool2_fwd', _code(dtype), C.c_void_p(x_ptr), x_pad, _p(obuf), 1, B, H, W, Cc, _stream())
-        ctx.saved = (keep, x_ptr, x_pad, (B, Cc, H, W), dtype)
-        ctx.x_like = x
-        return out
-
-    @staticmethod
-    def backward(ctx, dz):
-        keep, x_ptr, x_pad, (B, Cc, H, W), dtype = ctx.saved
-        keep_dz, dz_ptr = to_dense(dz, dtype)
-        dxb = torch.empty((B, H, W, Cc), dtype=dtype, device=dz.device)
-        _lib.call('fva_maxpool2_bwd', _code(dtype), C.c_void_p(dz_ptr), C.c_void_p(x_ptr), x_pad, _p(dxb), B, H, W, Cc, _stream())
-        return _grad_like(dxb, ctx.x_like), None
-
-
 def conv_bias_relu(x, conv, dtype=None):
     """``relu(conv(x))`` for an ``nn.Conv2d(Cin, Cout, 3, stride 1, padding 1, bias=True)`` (vgg.py's block)."""
     if conv.kernel_size != (3, 3) or conv.stride != (1, 1) or conv.padding != (1, 1) or conv.bias is None:
@@ -94,7 +74,7 @@ def conv_bias_relu(x, conv, dtype=None):
 
 def max_pool2(x, dtype=None):
     """``nn.MaxPool2d(kernel_size=2, stride=2)``"""
-    return MaxPool2Fn.apply(x, dtype or get_compute_dtype())
+    return MaxPoolFn.apply(x, dtype or get_compute_dtype(), 'max_pool2', 'fva_maxpool2_fwd', 'fva_maxpool2_bwd', lambda n: n // 2)
 
 
 def _pad_rgb(x, weight, dtype):
@@ -112,87 +92,6 @@ def _pad_rgb(x, weight, dtype):
         buf[:, 1:-1, 1:-1, :cin] = x.permute(0, 2, 3, 1)
         x = buf[:, 1:-1, 1:-1, :].permute(0, 3, 1, 2)
     return x, weight
-
-
-class ConvBNReLUFn(torch.autograd.Function):
-    """``relu(bn(conv(x) + b))``.  The bias cancels in the training-mode output (the batch mean takes it away again), so the convolution
-    runs without it and the bias is accounted for where it stays visible: running_mean tracks mean(y) + b (fva_bn_bias_running_mean) and
-    the eval-mode shift is beta + (b - running_mean) * scale (fva_bn_eval_coeffs_bias).  Its gradient is the channel sum of dy, which the
-    BatchNorm backward makes zero up to rounding: returned as exact zeros (a real fp32 tensor, for optimizers with weight decay).
-    With frozen statistics (the BatchNorm in eval mode, gradients on) nothing cancels: u = (y + b - running_mean) * scale_bn + beta, the
-    one-pass backward (ops.frozen_bn_bwd, ReLU form) takes m = running_mean - b, and dbias = scale * sum dU is a real gradient."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, gamma, beta, bn, training, dtype):
-        require_gpu(x, 'conv_bn_relu')
-        flush_pending_apply()
-        lib = _lib.load()
-        B, Cin, H, W = x.shape
-        Cout, dev, code = weight.shape[0], x.device, _code(dtype)
-        keep, x_ptr, x_pad = to_halo(x.detach(), dtype, 1)
-        d = _lib.ConvDesc(code, B, H, W, Cin, Cout, 3, 1, x_pad, 1)
-        wf, wd = packed_weights(weight, d, dtype, cache=weight.is_leaf)
-        M = B * H * W
-        y = torch.empty((M, Cout), dtype=dtype, device=dev)
-        scale = torch.empty(Cout, dtype=torch.float32, device=dev)
-        shift = torch.empty_like(scale)
-        b32 = bias.detach().float().contiguous()
-        mean = rstd = None
-        if training:
-            nblk = lib.fva_conv_stat_blocks(C.byref(d))
-            stats = torch.empty((lib.fva_bn_partial_rows(nblk), 2, Cout), dtype=torch.float32, device=dev)
-            mean, rstd = torch.empty_like(scale), torch.empty_like(scale)
-            _lib.call('fva_conv_fwd', C.byref(d), C.c_void_p(x_ptr), _p(wf), _p(y), _p(stats), _stream())
-            _lib.call('fva_bn_finalize', _p(stats), nblk, stats.shape[0], M, Cout, _p(gamma), _p(beta), _p(bn.rm), _p(bn.rv), _p(bn.nbt),
-                      bn.momentum, bn.eps, _p(mean), _p(rstd), _p(scale), _p(shift), _stream())
-            if bn.rm is not None:
-                _lib.call('fva_bn_bias_running_mean', Cout, _p(bn.rm), _p(b32), bn.momentum, _stream())
-        else:
-            if bn.rm is None:
-                raise RuntimeError('conv_bn_relu: eval mode needs running statistics (track_running_stats=True)')
-            _lib.call('fva_conv_fwd', C.byref(d), C.c_void_p(x_ptr), _p(wf), _p(y), C.c_void_p(0), _stream())
-            _lib.call('fva_bn_eval_coeffs_bias', Cout, _p(gamma), _p(beta), _p(bn.rm), _p(bn.rv), _p(b32), bn.eps, _p(scale), _p(shift), _stream())
-        zbuf, z = halo_alloc(B, Cout, H, W, dtype, dev, 1)
-        _lib.call('fva_bn_relu_apply', code, _p(y), _p(scale), _p(shift), _p(zbuf), 1, B, H, W, Cout, _stream())
-        need = training or any(ctx.needs_input_grad)
-        ctx.saved = (keep, x_ptr, y, scale, shift, mean, rstd, d, wd, dtype, tuple(weight.shape), gamma) if need else None
-        ctx.training, ctx.bn, ctx.b32 = training, (None if training else bn), (None if training else b32)
-        ctx.x_like, ctx.weight = x, weight
-        return z
-
-    @staticmethod
-    def backward(ctx, dz):
-        if ctx.saved is None:
-            raise _released('conv_bn_relu')
-        keep, x_ptr, y, scale, shift, mean, rstd, d, wd, dtype, wshape, gamma = ctx.saved
-        lib = _lib.load()
-        B, H, W, Cout, dev, code = d.B, d.H, d.W, d.Cout, y.device, _code(dtype)
-        M = B * H * W
-        keep_dz, dz_ptr = to_dense(dz, dtype)
-        if not ctx.training:
-            # frozen statistics: one pass, and only what autograd asks for
-            need_x, need_w, need_bias, need_g, need_b = ctx.needs_input_grad[:5]
-            dy = torch.empty((B, H + 2, W + 2, Cout), dtype=dtype, device=dev)
-            dgamma, dbeta, dbias = frozen_bn_bwd('relu', code, dz_ptr, y, scale, shift, ctx.bn, ctx.b32, dy, 1, B, H, W, Cout, need_g, need_b, need_bias)
-            dxb, dw = _wgrad_dgrad(d, x_ptr, dy, wd, wshape, (keep,), ctx.weight, need_x, need_dw=need_w)
-            dx = _grad_like(dxb, ctx.x_like) if dxb is not None else None
-            ctx.saved = ctx.x_like = ctx.weight = ctx.bn = ctx.b32 = None
-            return dx, dw, dbias, dgamma, dbeta, None, None, None
-        nb = lib.fva_bn_bwd_blocks(code, M, Cout)
-        part = torch.empty((lib.fva_bn_partial_rows(nb), 2, Cout), dtype=torch.float32, device=dev)
-        _lib.call('fva_bn_relu_bwd_reduce', code, C.c_void_p(dz_ptr), _p(y), _p(scale), _p(shift), _p(mean), _p(rstd), _p(part), nb, M, Cout, _stream())
-        dgamma = torch.empty(Cout, dtype=torch.float32, device=dev)
-        dbeta = torch.empty_like(dgamma)
-        coef = torch.empty((3, Cout), dtype=torch.float32, device=dev)
-        _lib.call('fva_bn_bwd_finalize', _p(part), nb, part.shape[0], M, Cout, _p(gamma), _p(rstd), _p(dgamma), _p(dbeta), 0, _p(coef), _stream())
-        dy = torch.empty((B, H + 2, W + 2, Cout), dtype=dtype, device=dev)
-        _lib.call('fva_bn_relu_bwd_apply', code, C.c_void_p(dz_ptr), _p(y), _p(scale), _p(shift), _p(mean), _p(rstd), _p(coef), _p(dy), 1,
-                  B, H, W, Cout, _stream())
-        dxb, dw = _wgrad_dgrad(d, x_ptr, dy, wd, wshape, (keep,), ctx.weight, ctx.needs_input_grad[0])
-        dx = _grad_like(dxb, ctx.x_like) if dxb is not None else None
-        dbias = torch.zeros(Cout, dtype=torch.float32, device=dev)
-        ctx.saved = ctx.x_like = ctx.weight = None          # released by the backward pass that used them
-        return dx, dw, dbias, dgamma, dbeta, None, None, None
 
 
 class AdaptiveAvgPool7FlattenFn(torch.autograd.Function):
@@ -222,14 +121,10 @@ def conv_bn_relu(x, conv, bn, dtype=None):
     module's ``training`` flag, momentum and eps are read at call time, its running statistics are updated in place on the device."""
     if conv.kernel_size != (3, 3) or conv.stride != (1, 1) or conv.padding != (1, 1) or conv.bias is None:
         raise RuntimeError('conv_bn_relu: only the VGG block (3x3, stride 1, padding 1, bias) is on this path')
-    if not bn.affine:
-        raise RuntimeError('conv_bn_relu: the BatchNorm2d must be affine')
-    if bn.training and bn.momentum is None and bn.track_running_stats:
-        raise RuntimeError('conv_bn_relu: momentum=None (cumulative average) is not on this path')
+    training = _check_bn(bn, 'conv_bn_relu')
     dtype = dtype or get_compute_dtype()
     x, weight = _pad_rgb(x, conv.weight, dtype)
-    training = bn.training or not bn.track_running_stats
-    return ConvBNReLUFn.apply(x, weight, conv.bias, bn.weight, bn.bias, _BNState(bn), training, dtype)
+    return ConvBNReLUFn.apply(x, weight, conv.bias, bn.weight, bn.bias, _BNState(bn), training, dtype, PlainConv(3, 1), None, torch.is_grad_enabled())
 
 
 def adaptive_avg_pool7_flatten(x, dtype=None):
