@@ -24,7 +24,7 @@ PER_FILE = {'colour.hip': ['-ffp-contract=off'], 'loss.hip': ['-ffp-contract=off
 
 
 def _newer(src, obj):
-    deps = [src, os.path.join(HERE, 'common.h'), os.path.join(ROOT, 'include', 'fastvision_amd.h')]
+    deps = [src, os.path.join(HERE, 'common.h'), os.path.join(HERE, 'multi_tensor.h'), os.path.join(ROOT, 'include', 'fastvision_amd.h')]
     return (not os.path.exists(obj)) or any(os.path.getmtime(d) > os.path.getmtime(obj) for d in deps)
 
 

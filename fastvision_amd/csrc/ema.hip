@@ -8,10 +8,10 @@
 #include <math.h>
 
 #include "common.h"
+#include "multi_tensor.h"
 
 namespace {
 
-constexpr int EMA_CHUNK = 16384;        // fp32 elements per block (64 KiB of each tensor): 16 float4 iterations of 256 threads
 constexpr int EMA_THREADS = 256;
 constexpr int EMA_COPY = 1;             // kind 1: raw copy; kind 0: fp32 lerp
 
@@ -29,18 +29,18 @@ __device__ __forceinline__ f32x4 ema_lerp4(f32x4 e, f32x4 p, float w) {
     return e;
 }
 
-// tab: int64 [4][n] = EMA tensor | model tensor | count | kind.  chunks: (tensor << 32) | chunk number; a chunk is EMA_CHUNK fp32
-// elements of a kind-0 tensor (count in elements) or 4 * EMA_CHUNK bytes of a kind-1 tensor (count in bytes).
+// tab: int64 [4][n] = EMA tensor | model tensor | count | kind.  chunks: one word per block (multi_tensor.h); a chunk is MT_CHUNK fp32
+// elements of a kind-0 tensor (count in elements) or 4 * MT_CHUNK bytes of a kind-1 tensor (count in bytes).
 __global__ __launch_bounds__(EMA_THREADS) void ema_kernel(const int64_t* __restrict__ tab, int n, const int64_t* __restrict__ chunks,
                                                           const double* __restrict__ state) {
     const int64_t word = chunks[blockIdx.x];
-    const int64_t t = word >> 32, c = word & 0xffffffffll;
+    const int64_t t = mt_tensor(word), c = mt_number(word);
     const int64_t count = tab[2 * n + t];
     if (tab[3 * n + t] == EMA_COPY) {
         unsigned char* __restrict__ dst = (unsigned char*)tab[t];
         const unsigned char* __restrict__ src = (const unsigned char*)tab[n + t];
-        const int64_t begin = c * (4 * (int64_t)EMA_CHUNK);
-        const int64_t end = begin + 4 * (int64_t)EMA_CHUNK < count ? begin + 4 * (int64_t)EMA_CHUNK : count;
+        const MtSpan s = mt_span(c, count, 4 * (int64_t)MT_CHUNK);
+        const int64_t begin = s.begin, end = s.end;
         int64_t i = begin;
         if ((((uintptr_t)dst | (uintptr_t)src) & 15) == 0 && end > begin) {
             const int64_t vend = begin + ((end - begin) & ~(int64_t)15);
@@ -53,8 +53,8 @@ __global__ __launch_bounds__(EMA_THREADS) void ema_kernel(const int64_t* __restr
     const float w = (float)state[1];
     float* __restrict__ e = (float*)tab[t];
     const float* __restrict__ p = (const float*)tab[n + t];
-    const int64_t begin = c * EMA_CHUNK;
-    const int64_t end = begin + EMA_CHUNK < count ? begin + EMA_CHUNK : count;
+    const MtSpan s = mt_span(c, count, MT_CHUNK);
+    const int64_t begin = s.begin, end = s.end;
     int64_t i = begin;
     if ((((uintptr_t)e | (uintptr_t)p) & 15) == 0 && end > begin) {
         constexpr int64_t STEP = 4 * EMA_THREADS;
@@ -81,7 +81,7 @@ __global__ __launch_bounds__(EMA_THREADS) void ema_kernel(const int64_t* __restr
 
 }  // namespace
 
-extern "C" int fva_ema_chunk_elems(void) { return EMA_CHUNK; }
+extern "C" int fva_ema_chunk_elems(void) { return MT_CHUNK; }
 
 extern "C" int fva_ema_update(const int64_t* tab_dev, int32_t n, const int64_t* chunks_dev, int32_t nchunks, double decay, double tau,
                               double* state_dev, void* stream) {

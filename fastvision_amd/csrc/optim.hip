@@ -7,11 +7,12 @@
 //
 // Multi-tensor SGD (torch.optim.SGD, single-tensor path of torch/optim/sgd.py) with the Faster R-CNN demo's global-norm clipping
 // (demos/faster_rcnn/cfg/_fit.py:6-17) on the device: grad_sqnorm_partial -> clip_coef -> sgd_kernel.  The work is split into
-// fixed-size chunks of SGD_CHUNK elements (one block per chunk, host-built chunk table), not into tensors, so one 103 M-element
+// fixed-size chunks of MT_CHUNK elements (one block per chunk, host-built chunk table), not into tensors, so one 103 M-element
 // tensor (VGG fc6) spreads over every CU instead of over blockIdx.x of one tensor.
 #include <math.h>
 
 #include "common.h"
+#include "multi_tensor.h"
 
 namespace {
 
@@ -86,10 +87,9 @@ __global__ __launch_bounds__(256) void gather_cast_kernel(const int64_t* __restr
 
 // ---- SGD --------------------------------------------------------------------------------------------------------------------
 // tab: int64 [6][n] = param | grad | momentum buffer (0: none) | element count | group index | slot in the fresh-flag array.
-// chunks: int64 [nchunks] = (tensor << 32) | chunk number; the chunk covers elements [c * SGD_CHUNK, min((c + 1) * SGD_CHUNK, size)).
+// chunks: int64 [nchunks], one word per block (multi_tensor.h): chunks of MT_CHUNK elements.
 // hyper: float [G][SGD_HYPER] = lr, weight decay, momentum, 1 - dampening, nesterov (0 / 1), one row per parameter group.
 // fresh: int32 per slot; non-zero = the momentum buffer has no history yet (torch's `buf = clone(grad)`).
-constexpr int SGD_CHUNK = 16384;        // 64 KiB of fp32 per block: 16 float4 iterations of 256 threads
 constexpr int SGD_THREADS = 256;
 constexpr int SGD_HYPER = 5;
 
@@ -97,12 +97,11 @@ struct SgdChunk {
     int64_t t, begin, end;
 };
 __device__ __forceinline__ SgdChunk sgd_chunk(const int64_t* __restrict__ tab, int n, const int64_t* __restrict__ chunks) {
-    const int64_t e = chunks[blockIdx.x];
+    const int64_t word = chunks[blockIdx.x];
     SgdChunk c;
-    c.t = e >> 32;
-    c.begin = (e & 0xffffffffll) * SGD_CHUNK;
-    const int64_t size = tab[3 * n + c.t];
-    c.end = c.begin + SGD_CHUNK < size ? c.begin + SGD_CHUNK : size;
+    c.t = mt_tensor(word);
+    c.begin = mt_number(word) * MT_CHUNK;
+    c.end = mt_end(c.begin, tab[3 * n + c.t], MT_CHUNK);
     return c;
 }
 
@@ -257,7 +256,7 @@ extern "C" int fva_adam_step_dev(const void* const* ptrs, const int64_t* sizes, 
     return FVA_OK;
 }
 
-extern "C" int fva_sgd_chunk_elems(void) { return SGD_CHUNK; }
+extern "C" int fva_sgd_chunk_elems(void) { return MT_CHUNK; }
 
 extern "C" int fva_sgd_clip_coef(const int64_t* tab_dev, int32_t n, const int64_t* chunks_dev, int32_t nchunks, double* partial_dev,
                                  double clip_norm, float* out_dev, void* stream) {

@@ -24,6 +24,7 @@ from copy import deepcopy
 import torch
 
 from . import _lib
+from .multi_tensor import WordTable, chunk_words, chunks_of, upload_words
 from .ops import _stream, require_gpu
 
 __all__ = ['ModelEMA']
@@ -47,11 +48,12 @@ def _unwrap(model):
     return model.module if is_parallel(model) else model
 
 
-def build_tables(pairs):
+def build_tables(pairs, table=None, key=None):
     """The device tables of ``fva_ema_update`` for ``pairs`` = [(name, EMA tensor, model tensor)]: (table int64 [4][n] = EMA pointer |
-    model pointer | count | kind, n, chunk table, nchunks, the pinned host words -- keep them alive until the upload has run).  fp32
-    pairs are averaged (kind 0, count in elements), all others copied (kind 1, count in bytes); pairs whose EMA tensor was already
-    listed (tied tensors appear under several keys) and empty tensors are left out."""
+    model pointer | count | kind, n, chunk table, nchunks, the host words or None), uploaded at once or through the WordTable ``table``
+    (cached by ``key``).  fp32 pairs are averaged (kind 0, count in elements), all others copied (kind 1, count in bytes, four times
+    as many to a chunk); pairs whose EMA tensor was already listed (tied tensors appear under several keys) and empty tensors are
+    left out."""
     per = _lib.call('fva_ema_chunk_elems')
     rows, seen = [], set()
     for k, e, p in pairs:
@@ -66,16 +68,14 @@ def build_tables(pairs):
             continue
         seen.add(e.data_ptr())
         if e.dtype == torch.float32:
-            rows.append((e.data_ptr(), p.data_ptr(), e.numel(), 0, (e.numel() + per - 1) // per))
+            rows.append((e.data_ptr(), p.data_ptr(), e.numel(), 0, per))
         else:
-            nbytes = e.numel() * e.element_size()
-            rows.append((e.data_ptr(), p.data_ptr(), nbytes, 1, (nbytes + 4 * per - 1) // (4 * per)))
+            rows.append((e.data_ptr(), p.data_ptr(), e.numel() * e.element_size(), 1, 4 * per))
     if not rows:
         raise RuntimeError('ModelEMA: nothing to average')
-    n = len(rows)
-    words = [r[c] for c in range(4) for r in rows] + [(t << 32) | c for t, r in enumerate(rows) for c in range(r[4])]
-    host = torch.tensor(words, dtype=torch.int64).pin_memory()
-    both = host.to(pairs[0][1].device, non_blocking=True)
+    n, dev = len(rows), pairs[0][1].device
+    words = [r[c] for c in range(4) for r in rows] + chunk_words(chunks_of(r[2], r[4]) for r in rows)
+    host, both = upload_words(words, dev) if table is None else (None, table.get(key, lambda: words, dev))
     return both[:4 * n], n, both[4 * n:], len(words) - 4 * n, host
 
 
@@ -103,6 +103,7 @@ class ModelEMA:
         self._state = torch.tensor([float(int(updates)), 1.0], dtype=torch.float64).to(self._device)      # updates done | weight of the last update
         self._own = None          # tensors of the averaged model, in state-dict order (they keep their addresses)
         self._tab = None          # the device tables of the last pairing (see _table)
+        self._words = WordTable('ModelEMA: run at least one eager update(model) before capturing a graph')      # no staging: see begin_capture
 
     # ---- the ramp ----------------------------------------------------------------------------------------------------
     def weight(self, k):
@@ -140,16 +141,9 @@ class ModelEMA:
             raise RuntimeError(f'ModelEMA.update: the model has no state-dict entry {missing[0]!r}')
         pairs = [(k, e, theirs[k]) for k, e in own.items()]
         key = [e.data_ptr() for _, e, _ in pairs] + [p.data_ptr() for _, _, p in pairs]
-        sig = [(p.shape, p.dtype) for _, _, p in pairs]
-        if hit is not None and hit['key'] == key and hit['sig'] == sig and hit['model']() is base:
-            # other tensor objects over the same memory: the tables hold; remember the new objects for the quick check
-            hit['theirs'] = [p for _, _, p in pairs]
-            hit['slots'] = _slots_of(base, hit['theirs'])
-            return hit
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError('ModelEMA: run at least one eager update(model) before capturing a graph')
-        tab, n, chunks, nchunks, host = build_tables(pairs)
-        self._tab = {'key': key, 'sig': sig, 'tab': tab, 'n': n, 'chunks': chunks, 'nchunks': nchunks, 'host': host, 'model': weakref.ref(base),
+        # other tensor objects over the same memory, shapes and types find the device words cached: only the quick check's objects change
+        tab, n, chunks, nchunks, _ = build_tables(pairs, self._words, (key, [(p.shape, p.dtype) for _, _, p in pairs]))
+        self._tab = {'key': key, 'tab': tab, 'n': n, 'chunks': chunks, 'nchunks': nchunks, 'model': weakref.ref(base),
                      'own': [e for _, e, _ in pairs], 'theirs': [p for _, _, p in pairs], 'slots': _slots_of(base, [p for _, _, p in pairs])}
         return self._tab
 
@@ -177,6 +171,11 @@ class ModelEMA:
         self._own = None
 
     # ---- graphs.GraphedTrainStep -------------------------------------------------------------------------------------
+    def begin_capture(self):
+        """What a graph that captures ``update`` must keep alive: the device tables of the last eager update.  They are built once
+        per pairing and never rewritten, so graphs share them and there is no staging ("Multi-tensor tables")."""
+        return [] if self._tab is None else [self._tab['tab'], self._tab['chunks']]
+
     def snapshot_state(self):
         """A device copy of the averaged model's tensors and of the device counter."""
         return {'tensors': [t.detach().clone() for t in self._tensors().values()], 'state': self._state.clone()}

@@ -81,7 +81,7 @@ class GraphedTrainStep:
     priority and takes CUs from the critical path -- 43-44 ms instead of 32 per YOLOv3 step (the eager
     step's side stream is low-priority, which graph kernel nodes cannot be on this runtime) -- so the library's side stream is
     switched off around warm-up and capture and put back afterwards; pass True to capture the two-branch form anyway.
-    Several graphs may be captured on one optimizer (another batch size, a re-capture): each owns its pointer-table staging.
+    Several graphs may be captured on one optimizer (another batch size, a re-capture): each owns its table staging.
     ``ema`` (ModelEMA, optional): ``ema.update(model)`` follows the optimizer step inside the captured sequence -- its update counter and
     weight live on the device, so each replay applies the next point of the ramp; warm-up and capture leave the average and its
     counter untouched, and after each replay the versions of the averaged model's tensors are advanced.
@@ -135,7 +135,9 @@ class GraphedTrainStep:
             optimizer.zero_grad(set_to_none=True)
             torch.autograd.graph.increment_version(self.params)      # the captured sequence must start with the weight re-pack
             host_before = optimizer.host_state()                    # e.g. Adam's step counts
-            self._adam_staging = optimizer.begin_capture()           # this graph's own pointer-table words (kept alive with it)
+            # kept alive with the graph ("Multi-tensor tables"): this graph's own table staging of the optimizer, whichever
+            # it is (the name is older than FusedSGD), and the average's tables
+            self._adam_staging, self._ema_tables = optimizer.begin_capture(), ema.begin_capture() if ema is not None else []
             if on_capture is not None:
                 on_capture()                                         # e.g. arm the library's event spans: they become graph nodes
             self.graph = torch.cuda.CUDAGraph()
@@ -147,7 +149,6 @@ class GraphedTrainStep:
         torch.autograd.graph.increment_version(self.params)
         if ema is not None:
             ema.bump_versions()
-            self._ema_tables = ema._tab                              # the captured launch reads these device tables: kept alive with the graph
         self.replays = 0
 
     def _step(self):

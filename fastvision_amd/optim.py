@@ -15,23 +15,40 @@ import ctypes as C
 import torch
 
 from . import _lib
-from .ops import _stream
+from .multi_tensor import WordTable, capturing, chunk_words, chunks_of, upload_words
+from .ops import _stream, join_side_stream
 
 __all__ = ['FusedAdam', 'FusedSGD']
 
 
-class FusedAdam(torch.optim.Optimizer):
+class _FusedOptimizer(torch.optim.Optimizer):
+    """The frame of ``step()`` that the two optimizers share; ``_launch()`` returns the parameters its kernels wrote."""
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        join_side_stream()          # weight gradients may still be in flight on the library's side stream
+        torch.autograd.graph.increment_version(self._launch())      # written in place: invalidate packed-weight caches
+        return loss
+
+
+class FusedAdam(_FusedOptimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, grad_scale=1.0, capturable=False):
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         self.grad_scale = grad_scale
         self.capturable = capturable
-        self._tables = {}
-        self._dev = {}            # group index -> {'state': double[3], 'lr': float[1], 'lr_host': float, 'pinned': int64[5n], 'table': int64[5n]}
+        self._tables = {}         # group index -> WordTable of [4][n] pointers + sizes
+        self._max = {}            # group index -> largest tensor of that table
+        self._dev = {}            # group index -> {'state': double[3], 'lr': float[1], 'lr_host': float}
 
     # ---- checkpoints -------------------------------------------------------------------------------------------------
     def load_state_dict(self, state_dict):
         super().load_state_dict(state_dict)
-        self._tables.clear()                      # the moment tensors were replaced: pointer tables are stale
+        for t in self._tables.values():           # the moment tensors were replaced: pointer tables are stale
+            t.invalidate()
         for gi, d in self._dev.items():           # device step counters follow the loaded step
             ps = [p for p in self.param_groups[gi]['params'] if p in self.state and self.state[p]]
             if ps:
@@ -44,7 +61,9 @@ class FusedAdam(torch.optim.Optimizer):
 
     # ---- pointer table -----------------------------------------------------------------------------------------------
     def _table(self, gi, group):
-        """Device pointer table [4][n] + sizes, rebuilt only when a parameter, gradient or moment tensor moved."""
+        """(parameters with a gradient, device words [4][n] = param | grad | exp_avg | exp_avg_sq followed by n sizes, n, largest
+        size), rebuilt only when a parameter, gradient or moment tensor moved.  Gradients are fresh tensors every step, so eager
+        training re-uploads this small table every step."""
         ps = [p for p in group['params'] if p.grad is not None]
         for p in ps:
             st = self.state[p]
@@ -56,51 +75,20 @@ class FusedAdam(torch.optim.Optimizer):
                 raise RuntimeError('FusedAdam needs contiguous fp32 parameters and gradients')
         key = tuple((p.data_ptr(), p.grad.data_ptr(), self.state[p]['exp_avg'].data_ptr(), self.state[p]['exp_avg_sq'].data_ptr())
                     for p in ps)
-        hit = self._tables.get(gi)
-        if hit is None or hit[0] != key:
-            n = len(ps)
-            vals = [k[0] for k in key] + [k[1] for k in key] + [k[2] for k in key] + [k[3] for k in key] + [p.numel() for p in ps]
-            dev = ps[0].device
-            if dev.type == 'cuda' and torch.cuda.is_current_stream_capturing():
-                # inside a graph capture nothing may be allocated on the host side: the staging buffers were made by an eager
-                # (warm-up) step; the captured copy node re-reads the same pinned words on every replay
-                d = self._dev.get(gi)
-                if d is None or d.get('pinned') is None or d['pinned'].numel() != len(vals):
-                    raise RuntimeError('FusedAdam: run at least one eager step() (capturable=True) and begin_capture() before capturing a graph')
-                host, both = d['pinned'], d['table']
-                host.copy_(torch.tensor(vals, dtype=torch.int64))
-                both.copy_(host, non_blocking=True)
-            else:
-                # gradients are fresh tensors every step, so this small table is re-uploaded every step: pinned staging +
-                # non_blocking keeps the upload asynchronous (a pageable .to(device) would stall the host on the stream)
-                host = torch.tensor(vals, dtype=torch.int64)
-                if dev.type == 'cuda':
-                    host = host.pin_memory()
-                both = host.to(dev, non_blocking=True)
-                if self.capturable and dev.type == 'cuda':
-                    d = self._dev_state(gi, group, dev)
-                    if d.get('pinned') is None or d['pinned'].numel() != len(vals):
-                        d['pinned'] = torch.empty(len(vals), dtype=torch.int64).pin_memory()
-                        d['table'] = torch.empty(len(vals), dtype=torch.int64, device=dev)
-            tab, sizes = both[:4 * n], both[4 * n:]
-            hit = (key, tab, sizes, n, max(p.numel() for p in ps), host)
-            self._tables[gi] = hit
-        return ps, hit
+
+        def words():
+            sizes = [p.numel() for p in ps]
+            self._max[gi] = max(sizes)
+            return [k[c] for c in range(4) for k in key] + sizes
+
+        if gi not in self._tables:
+            self._tables[gi] = WordTable('FusedAdam: run at least one eager step() (capturable=True) and begin_capture() before '
+                                         'capturing a graph', self.capturable)
+        return ps, self._tables[gi].get(key, words, ps[0].device), len(ps), self._max[gi]
 
     def begin_capture(self):
-        """Fresh staging buffers for ONE graph capture (call right before ``torch.cuda.graph``, after a warm-up step).  The captured
-        copy node re-reads the pinned words it was recorded with on every replay, so every graph needs words of its own: with one
-        shared buffer a second capture on the same optimizer (another batch size, a re-capture) rewrote the pointers the first
-        graph's Adam launch reads.  Returns the buffers: the graph's owner keeps them alive as long as the graph."""
-        owned = []
-        for gi, d in self._dev.items():
-            if d.get('pinned') is not None:
-                n = d['pinned'].numel()
-                d['pinned'] = torch.empty(n, dtype=torch.int64).pin_memory()
-                d['table'] = torch.empty(n, dtype=torch.int64, device=d['state'].device)
-                owned.append((d['pinned'], d['table']))
-        self._tables.clear()              # the capture-time step must write (and record the upload of) its own table
-        return owned
+        """This graph's own staging for every group's table, as [(pinned, device)] ("Multi-tensor tables")."""
+        return [s for t in self._tables.values() for s in t.begin_capture()]
 
     def _dev_state(self, gi, group, dev):
         d = self._dev.get(gi)
@@ -165,39 +153,34 @@ class FusedAdam(torch.optim.Optimizer):
         for p, k in saved:
             self.state[p]['step'] = k
 
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        from .ops import join_side_stream
-        join_side_stream()          # weight gradients may still be in flight on the library's side stream
+    def _launch(self):
+        written = []
         for gi, group in enumerate(self.param_groups):
             if not any(p.grad is not None for p in group['params']):
                 continue
-            ps, (_, tab, sizes, n, mx, _keep) = self._table(gi, group)
+            ps, words, n, mx = self._table(gi, group)
             if not ps[0].is_cuda:
                 raise RuntimeError('FusedAdam: parameters must live on the GPU (no CPU path)')
+            tab, sizes = C.c_void_p(words.data_ptr()), C.c_void_p(words.data_ptr() + 32 * n)
+            d = self._dev_state(gi, group, ps[0].device) if self.capturable else None     # starts from the host step count: before it moves
             step = self._step_of(ps[0]) + 1
             for p in ps:
                 self.state[p]['step'] = step
             b1, b2 = group['betas']
             if self.capturable:
-                d = self._dev_state(gi, group, ps[0].device)
-                if not torch.cuda.is_current_stream_capturing() and d['lr_host'] != group['lr']:
+                if not capturing(ps[0].device) and d['lr_host'] != group['lr']:
                     d['lr'].fill_(float(group['lr']))
                     d['lr_host'] = group['lr']
-                _lib.call('fva_adam_step_dev', C.c_void_p(tab.data_ptr()), C.c_void_p(sizes.data_ptr()), n, mx, C.c_void_p(d['lr'].data_ptr()),
+                _lib.call('fva_adam_step_dev', tab, sizes, n, mx, C.c_void_p(d['lr'].data_ptr()),
                           b1, b2, group['eps'], group['weight_decay'], C.c_void_p(d['state'].data_ptr()), self.grad_scale, _stream())
             else:
-                _lib.call('fva_adam_step', C.c_void_p(tab.data_ptr()), C.c_void_p(sizes.data_ptr()), n, mx, group['lr'], b1, b2,
+                _lib.call('fva_adam_step', tab, sizes, n, mx, group['lr'], b1, b2,
                           group['eps'], group['weight_decay'], step, self.grad_scale, _stream())
-            torch.autograd.graph.increment_version(ps)      # the kernel wrote p in place: invalidate packed-weight caches
-        return loss
+            written += ps
+        return written
 
 
-class FusedSGD(torch.optim.Optimizer):
+class FusedSGD(_FusedOptimizer):
     """torch.optim.SGD semantics (the optimizer of the reference's Faster R-CNN demo, demos/faster_rcnn/train.py:91-109: momentum
     0.937, Nesterov, parameter groups) as ONE multi-tensor HIP launch per step for every group (``fva_sgd_step``), with the demo's
     gradient-norm clipping (cfg/_fit.py:6-17) optionally on the device.
@@ -213,10 +196,10 @@ class FusedSGD(torch.optim.Optimizer):
     rewritten (the reference scales it in place); ``last_grad_norm`` is the fp32 device scalar of the norm (overwritten by the next
     step).  A non-finite norm behaves as the reference: NaN gives NaN parameters, infinity a coefficient of 0.
 
-    ``capturable=True`` follows FusedAdam's protocol for graphs.GraphedTrainStep: the hyper-parameters (lr of each group) live in a
-    device table that ``step()`` / ``sync_lr()`` refresh when ``param_groups`` change, ``begin_capture()`` gives each graph its own
-    pointer-table staging, and at least one eager ``step()`` must run before a capture.  Whether a momentum buffer still has to be
-    initialised is a device flag, so a captured step restored to a fresh optimizer's state initialises it exactly once.
+    ``capturable=True`` serves graphs.GraphedTrainStep (the table protocol: DESIGN.md, "Multi-tensor tables"): the hyper-parameters
+    (lr of each group) live in a device table that ``step()`` / ``sync_lr()`` refresh when ``param_groups`` change, and at least one
+    eager ``step()`` must run before a capture.  Whether a momentum buffer still has to be initialised is a device flag, so a
+    captured step restored to a fresh optimizer's state initialises it exactly once.
     Parameters and gradients must be contiguous fp32 tensors on the GPU (no CPU path).  ``lr`` defaults to 1e-3 as in torch's SGD;
     ``maximize``, ``foreach``, ``fused`` and ``differentiable`` are accepted only at torch's defaults (False, None, None, False):
     any other value, ``foreach=False`` included, is refused rather than silently ignored.
@@ -243,12 +226,13 @@ class FusedSGD(torch.optim.Optimizer):
                                       maximize=False, foreach=None, differentiable=False, fused=None))
         self.clip_norm = None if clip_norm is None else float(clip_norm)
         self.capturable = capturable
-        self._tab = None          # (key, table, n, host words) of the last pointer table
-        self._chunks = None       # (sizes, chunk table, nchunks, fp64 partials)
+        self._tab = WordTable('FusedSGD: run at least one eager step() (capturable=True) and begin_capture() before capturing a graph',
+                              capturable)                                                              # [6][n], see _table
+        self._chunks = WordTable('FusedSGD: run at least one eager step() before capturing a graph')   # one word per block
+        self._partial = None      # device double per chunk: the clipping norm's partial sums
         self._hyper = None        # (host values, device float [G][5])
         self._fresh = None        # device int32 per parameter slot: the momentum buffer has no history yet
         self._clip_out = None     # device float [2]: norm, coefficient
-        self._stage = None        # capturable: (pinned words, device table) re-read by a captured copy node
 
     def __setstate__(self, state):
         super().__setstate__(state)
@@ -258,7 +242,7 @@ class FusedSGD(torch.optim.Optimizer):
     # ---- checkpoints -------------------------------------------------------------------------------------------------
     def load_state_dict(self, state_dict):
         super().load_state_dict(state_dict)
-        self._tab = None                          # the buffers were replaced: the pointer table is stale
+        self._tab.invalidate()                    # the buffers were replaced: the pointer table is stale
         for p, st in self.state.items():          # a loaded buffer has history (torch's SGD continues it)
             buf = st.get('momentum_buffer')
             if buf is not None and not buf.is_contiguous():
@@ -291,15 +275,10 @@ class FusedSGD(torch.optim.Optimizer):
         vals = tuple(vals)
         if self._hyper is not None and self._hyper[0] == vals:
             return
-        if torch.cuda.is_current_stream_capturing():
+        if capturing(dev):
             raise RuntimeError('FusedSGD: hyper-parameters changed during a graph capture; call sync_lr() before capturing')
-        host = torch.tensor(vals, dtype=torch.float32).pin_memory()
-        if self._hyper is not None and self._hyper[1].numel() == len(vals):
-            devt = self._hyper[1]
-        else:
-            devt = torch.empty(len(vals), dtype=torch.float32, device=dev)
-        devt.copy_(host, non_blocking=True)
-        self._hyper = (vals, devt, host)
+        same = self._hyper is not None and self._hyper[1].numel() == len(vals)       # captured steps read this address: refill it
+        self._hyper = (vals, upload_words(vals, dev, torch.float32, out=self._hyper[1] if same else None)[1])
 
     def sync_lr(self):
         """Refresh the device hyper-parameter table from param_groups (capturable mode; graphs.GraphedTrainStep calls it before each
@@ -307,20 +286,9 @@ class FusedSGD(torch.optim.Optimizer):
         if self._hyper is not None:
             self._sync_hyper(self._hyper[1].device)
 
-    def _chunk_table(self, sizes, dev):
-        if self._chunks is not None and self._chunks[0] == sizes:
-            return self._chunks
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError('FusedSGD: run at least one eager step() before capturing a graph')
-        per = _lib.call('fva_sgd_chunk_elems')
-        words = [(t << 32) | c for t, n in enumerate(sizes) for c in range((n + per - 1) // per)]
-        chunks = torch.tensor(words, dtype=torch.int64).pin_memory().to(dev, non_blocking=True)
-        partial = torch.empty(len(words), dtype=torch.float64, device=dev)
-        self._chunks = (sizes, chunks, len(words), partial)
-        return self._chunks
-
     def _table(self):
-        """Device table [6][n] of the parameters that have a gradient (all groups), rebuilt only when a pointer moved."""
+        """(parameters that have a gradient (all groups), their device table [6][n] = param | grad | momentum buffer (0: none) | size |
+        group | fresh-flag slot, n, chunk table, any momentum buffer), each table rebuilt only when its words changed."""
         ps, gids = [], []
         for gi, group in enumerate(self.param_groups):
             for p in group['params']:
@@ -338,54 +306,35 @@ class FusedSGD(torch.optim.Optimizer):
             return None
         dev = ps[0].device
         slots = self._slots(dev)
-        capturing = torch.cuda.is_current_stream_capturing()
         born = []
         for p, gi in zip(ps, gids):
             if self.param_groups[gi]['momentum'] != 0 and self.state[p].get('momentum_buffer') is None:
-                if capturing:
-                    raise RuntimeError('FusedSGD: run at least one eager step() (capturable=True) and begin_capture() before capturing a graph')
+                if capturing(dev):
+                    raise RuntimeError(self._tab.capture_error)
                 self.state[p]['momentum_buffer'] = torch.empty_like(p, memory_format=torch.contiguous_format)
                 born.append(slots[p])
         if born:                                  # their first update is torch's clone(grad)
-            idx = torch.tensor(born, dtype=torch.int64).pin_memory().to(dev, non_blocking=True)
-            self._fresh.index_fill_(0, idx, 1)
+            self._fresh.index_fill_(0, upload_words(born, dev)[1], 1)
         bufs = [self.state[p]['momentum_buffer'].data_ptr() if self.param_groups[gi]['momentum'] != 0 else 0 for p, gi in zip(ps, gids)]
         key = (tuple(p.data_ptr() for p in ps), tuple(p.grad.data_ptr() for p in ps), tuple(bufs), tuple(gids))
         sizes = tuple(p.numel() for p in ps)
-        chunks = self._chunk_table(sizes, dev)
-        if self._tab is None or self._tab[0] != key:
-            n = len(ps)
-            vals = list(key[0]) + list(key[1]) + list(key[2]) + list(sizes) + list(gids) + [slots[p] for p in ps]
-            if capturing:
-                # nothing may be allocated on the host during a capture: the staging words were made by an eager step; the captured
-                # copy node re-reads them on every replay
-                if self._stage is None or self._stage[0].numel() != len(vals):
-                    raise RuntimeError('FusedSGD: run at least one eager step() (capturable=True) and begin_capture() before capturing a graph')
-                host, tab = self._stage
-                host.copy_(torch.tensor(vals, dtype=torch.int64))
-                tab.copy_(host, non_blocking=True)
-            else:
-                host = torch.tensor(vals, dtype=torch.int64).pin_memory()
-                tab = host.to(dev, non_blocking=True)
-                if self.capturable and (self._stage is None or self._stage[0].numel() != len(vals)):
-                    self._stage = (torch.empty(len(vals), dtype=torch.int64).pin_memory(), torch.empty(len(vals), dtype=torch.int64, device=dev))
-            self._tab = (key, tab, n, host)
+
+        def chunk_table():
+            per = _lib.call('fva_sgd_chunk_elems')
+            words = chunk_words(chunks_of(n, per) for n in sizes)
+            self._partial = torch.empty(len(words), dtype=torch.float64, device=dev)
+            return words
+
+        chunks = self._chunks.get(sizes, chunk_table, dev)
+        tab = self._tab.get(key, lambda: [w for col in key[:3] for w in col] + list(sizes) + list(gids) + [slots[p] for p in ps], dev)
         # the device flags are the only record of which buffers still need torch's clone(grad): every update that has momentum
         # buffers clears the flags of its tensors afterwards (one tiny launch, idempotent), so eager steps, captured steps and
         # replays after restore_state() all agree without any host-side bookkeeping
-        clear = any(b != 0 for b in bufs)
-        return ps, self._tab[1], self._tab[2], chunks, clear
+        return ps, tab, len(ps), chunks, any(b != 0 for b in bufs)
 
     def begin_capture(self):
-        """Fresh staging words for ONE graph capture (call right before ``torch.cuda.graph``, after a warm-up step); the graph's owner
-        keeps the returned buffers alive as long as the graph (see FusedAdam.begin_capture)."""
-        owned = []
-        if self._stage is not None:
-            n = self._stage[0].numel()
-            self._stage = (torch.empty(n, dtype=torch.int64).pin_memory(), torch.empty(n, dtype=torch.int64, device=self._stage[1].device))
-            owned.append(self._stage)
-        self._tab = None                  # the capture-time step must write (and record the upload of) its own table
-        return owned
+        """This graph's own staging for the pointer table, as [(pinned, device)] ("Multi-tensor tables")."""
+        return self._tab.begin_capture()
 
     # ---- graphs.GraphedTrainStep --------------------------------------------------------------------------------------
     def snapshot_state(self):
@@ -425,30 +374,23 @@ class FusedSGD(torch.optim.Optimizer):
     def note_replayed_steps(self, k=1):
         pass
 
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        from .ops import join_side_stream
-        join_side_stream()          # weight gradients may still be in flight on the library's side stream
+    def _launch(self):
         got = self._table()
         if got is None:
-            return loss
-        ps, tab, n, (_, chunks, nchunks, partial), clear = got
+            return []
+        ps, tab, n, chunks, clear = got
         dev = ps[0].device
         self._sync_hyper(dev)
+        tab, chunks, nchunks = C.c_void_p(tab.data_ptr()), C.c_void_p(chunks.data_ptr()), chunks.numel()
         coef = C.c_void_p(0)
         if self.clip_norm is not None:
             if self._clip_out is None:
-                if torch.cuda.is_current_stream_capturing():
+                if capturing(dev):
                     raise RuntimeError('FusedSGD: run at least one eager step() before capturing a graph')
                 self._clip_out = torch.zeros(2, dtype=torch.float32, device=dev)
-            _lib.call('fva_sgd_clip_coef', C.c_void_p(tab.data_ptr()), n, C.c_void_p(chunks.data_ptr()), nchunks,
-                      C.c_void_p(partial.data_ptr()), self.clip_norm, C.c_void_p(self._clip_out.data_ptr()), _stream())
+            _lib.call('fva_sgd_clip_coef', tab, n, chunks, nchunks, C.c_void_p(self._partial.data_ptr()), self.clip_norm,
+                      C.c_void_p(self._clip_out.data_ptr()), _stream())
             coef = C.c_void_p(self._clip_out.data_ptr() + 4)
-        _lib.call('fva_sgd_step', C.c_void_p(tab.data_ptr()), n, C.c_void_p(chunks.data_ptr()), nchunks, C.c_void_p(self._hyper[1].data_ptr()),
-                  C.c_void_p(self._fresh.data_ptr()), 1 if clear else 0, coef, _stream())
-        torch.autograd.graph.increment_version(ps)      # the kernel wrote p in place: invalidate packed-weight caches
-        return loss
+        _lib.call('fva_sgd_step', tab, n, chunks, nchunks, C.c_void_p(self._hyper[1].data_ptr()), C.c_void_p(self._fresh.data_ptr()),
+                  1 if clear else 0, coef, _stream())
+        return ps
