@@ -249,12 +249,21 @@ PROTOTYPES = {
     'fva_gconv_dgrad': (_I, [_G, _P, _P, _P, _P]),
     'fva_gconv_wgrad': (_I, [_G, _P, _P, _P, _P, _L, _P]),
     'fva_gconv_wgrad_workspace': (_L, [_G]),
+    'fva_gconv_mfma_serves': (_I, [_G]),
+    'fva_gconv_mfma_pack_bytes': (_L, [_G]),
+    'fva_gconv_mfma_pack': (_I, [_G, _P, _P, _P, _P]),
+    'fva_gconv_mfma_stat_blocks': (_I, [_G]),
+    'fva_gconv_mfma_fwd': (_I, [_G, _P, _P, _P, _P, _P]),
+    'fva_gconv_mfma_dgrad': (_I, [_G, _P, _P, _P, _P]),
+    'fva_gconv_mfma_wgrad_workspace': (_L, [_G]),
+    'fva_gconv_mfma_wgrad': (_I, [_G, _P, _P, _P, _P, _L, _P]),
 }
 LABEL_I64, LABEL_F32 = 0, 1
 REDUCE_MEAN, REDUCE_SUM = 0, 1
 UNCHECKED = {'fva_conv_patch_kernel', 'fva_sgd_chunk_elems', 'fva_ema_chunk_elems', 'fva_rows_relu_bwd_rows', 'fva_colour_workspace', 'fva_conv_dgrad_stat_rows', 'fva_bias_relu_bwd_rows', 'fva_colsum_scratch_rows', 'fva_last_error', 'fva_version', 'fva_profile_stop', 'fva_conv_last_kernel', 'fva_conv_packed_elems', 'fva_conv_stat_blocks', 'fva_conv_wgrad_workspace', 'fva_conv_wgrad_plan',
              'fva_stem_stat_blocks', 'fva_stem_fused_blocks', 'fva_stem_wgrad_workspace', 'fva_stem_fwd_workspace', 'fva_stem_wgrad_mfma_workspace', 'fva_bn_bwd_blocks', 'fva_bn_partial_rows', 'fva_yolov3_loss_workspace',
-             'fva_demo_loss_workspace', 'fva_demo_ciou_loss_workspace', 'fva_nms_candidates_workspace', 'fva_nms_select_workspace', 'fva_softmax_ce_workspace', 'fva_bn_frozen_bwd_blocks', 'fva_stem7_kp', 'fva_bn_add_relu_bwd_blocks', 'fva_gconv_stat_blocks', 'fva_gconv_wgrad_workspace'}
+             'fva_demo_loss_workspace', 'fva_demo_ciou_loss_workspace', 'fva_nms_candidates_workspace', 'fva_nms_select_workspace', 'fva_softmax_ce_workspace', 'fva_bn_frozen_bwd_blocks', 'fva_stem7_kp', 'fva_bn_add_relu_bwd_blocks', 'fva_gconv_stat_blocks', 'fva_gconv_wgrad_workspace',
+             'fva_gconv_mfma_serves', 'fva_gconv_mfma_pack_bytes', 'fva_gconv_mfma_stat_blocks', 'fva_gconv_mfma_wgrad_workspace'}
 
 _lib = None
 

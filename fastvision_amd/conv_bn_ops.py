@@ -5,8 +5,8 @@ Conv2d -> BatchNorm2d -> ReLU layer, its pieces, and the one max-pool node.
                                  fva_bn_eval_coeffs, the BatchNorm + ReLU apply pass; backward = the two BatchNorm + ReLU passes (training) or the
                                  one-pass frozen-statistics backward (ops.frozen_bn_bwd), then the convolution's weight and data gradients.
                                  The convolution is a back end: PlainConv (implicit GEMM on the packed weights, 1x1 / 3x3, stride 1 / 2) or
-                                 GroupedConv (fva_gconv_* on the fp32 master weight).  A convolution bias (VGG) changes three launches and the
-                                 dbias rule, see the node's docstring
+                                 GroupedConv (fva_gconv_* on the fp32 master weight, or fva_gconv_mfma_* on its packed tables).  A convolution
+                                 bias (VGG) changes three launches and the dbias rule, see the node's docstring
     MaxPoolFn                    max_pool2 / max_pool3s2: two entry-point names and an output-size rule
     _conv_bn, _bn_relu_apply, _bn_relu_bwd, _bn_add_relu_bwd_identity, _block_bn_relu_bwd
                                  the pieces, also used by resnet_ops' stem and BatchNorm + add + ReLU tail
@@ -157,30 +157,45 @@ class PlainConv:
 
 
 class GroupedConv:
-    """``groups > 1``, 3x3: fva_gconv_fwd / _dgrad / _wgrad on the fp32 master weight (no packed copy, nothing registered with
-    ops._PackRegistry).  Its data gradient takes no addend: a tail's summand comes back through autograd."""
+    """``groups > 1``, 3x3.  ``path`` (resnet_ops.set_grouped_path) routes per layer:
+    'plain': fva_gconv_fwd / _dgrad / _wgrad on the fp32 master weight (no packed copy, nothing registered with ops._PackRegistry).
+    'mfma':  where fva_gconv_mfma_serves(d) == 1 (bf16, stride 1, border 1, a map that fits the staging) the matrix-unit kernels:
+             operands() launches fva_gconv_mfma_pack in front of every forward (not cached: a captured step replays it on the weights the
+             optimizer has just written) and the forward / backward take the two packed tables; every other layer takes the plain launches.
+    Its data gradient takes no addend: a tail's summand comes back through autograd."""
     k, fwd, blocks = 3, 'fva_gconv_fwd', 'fva_gconv_stat_blocks'
+    wgrad, wgrad_ws, dgrad = 'fva_gconv_wgrad', 'fva_gconv_wgrad_workspace', 'fva_gconv_dgrad'
 
-    def __init__(self, groups, stride):
-        self.groups, self.stride = groups, stride
+    def __init__(self, groups, stride, path='plain'):
+        self.groups, self.stride, self.path = groups, stride, path
 
     def operands(self, code, B, Cin, H, W, x_pad, weight, dtype):
         w = weight.detach()
         if w.dtype != torch.float32 or not w.is_contiguous():
             w = w.float().contiguous()
-        return _lib.GConvDesc(code, B, H, W, Cin, self.groups, self.stride, x_pad, 1), w, w
+        d = _lib.GConvDesc(code, B, H, W, Cin, self.groups, self.stride, x_pad, 1)
+        lib = _lib.load()
+        if self.path != 'mfma' or lib.fva_gconv_mfma_serves(C.byref(d)) != 1:
+            return d, w, w
+        self.fwd, self.blocks = 'fva_gconv_mfma_fwd', 'fva_gconv_mfma_stat_blocks'
+        self.wgrad, self.wgrad_ws, self.dgrad = 'fva_gconv_mfma_wgrad', 'fva_gconv_mfma_wgrad_workspace', 'fva_gconv_mfma_dgrad'
+        nb = lib.fva_gconv_mfma_pack_bytes(C.byref(d))
+        wf = torch.empty(nb, dtype=torch.uint8, device=w.device)
+        wb = torch.empty_like(wf)
+        _lib.call('fva_gconv_mfma_pack', C.byref(d), _p(w), _p(wf), _p(wb), _stream())
+        return d, wf, wb
 
     def backward(self, d, x_ptr, dy, w, wshape, keep, weight, need_x, need_w, addend):
         assert addend is None
         dw = dxb = None
         if need_w:
             dw = torch.empty(wshape, dtype=torch.float32, device=dy.device)
-            wsb = _lib.load().fva_gconv_wgrad_workspace(C.byref(d))
+            wsb = getattr(_lib.load(), self.wgrad_ws)(C.byref(d))
             ws = torch.empty(wsb, dtype=torch.uint8, device=dy.device)
-            _lib.call('fva_gconv_wgrad', C.byref(d), C.c_void_p(x_ptr), _p(dy), _p(dw), _p(ws), wsb, wgrad_stream((keep, dy, ws), weight))
+            _lib.call(self.wgrad, C.byref(d), C.c_void_p(x_ptr), _p(dy), _p(dw), _p(ws), wsb, wgrad_stream((keep, dy, ws), weight))
         if need_x:
             dxb = torch.empty((d.B, d.H, d.W, d.C), dtype=dy.dtype, device=dy.device)
-            _lib.call('fva_gconv_dgrad', C.byref(d), _p(dy), _p(w), _p(dxb), _stream())
+            _lib.call(self.dgrad, C.byref(d), _p(dy), _p(w), _p(dxb), _stream())
         return dxb, dw
 
 

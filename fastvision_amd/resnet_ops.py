@@ -6,7 +6,8 @@
     max_pool3s2(x)                   MaxPool2d(3, 2, 1); backward recomputes the first maximum from x
     conv_bn_relu(x, conv, bn)        bias-free Conv2d (1x1 s1, 3x3 s1, 3x3 s2) -> BatchNorm2d -> ReLU: conv_bn_ops.ConvBNReLUFn, the node that
                                      vgg_ops.conv_bn_relu runs too, without a bias; frozen statistics take the one-pass backward.  A grouped
-                                     3x3 (ResNeXt's conv2; GROUPED_CONTRACT) is the same node on conv_bn_ops.GroupedConv (fva_gconv_*)
+                                     3x3 (ResNeXt's conv2; GROUPED_CONTRACT) is the same node on conv_bn_ops.GroupedConv (fva_gconv_*, or
+                                     fva_gconv_mfma_* under set_grouped_path('mfma'))
     conv_bn_add_relu(x, conv, bn, identity)
     conv_bn_add_relu(x, conv, bn, shortcut_in, shortcut_conv, shortcut_bn)
                                      the tail of a residual block, relu(bn(conv(x)) + R) with the add INSIDE the ReLU, one autograd node:
@@ -34,7 +35,7 @@ from .conv_bn_ops import (WIDE_FROZEN, ConvBNReLUFn, GroupedConv, MaxPoolFn, Pla
 from .ops import (_BNState, _code, _grad_like, _p, _released, _stream, _wgrad_dgrad, flush_pending_apply, get_compute_dtype, halo_alloc,
                   packed_weights, require_gpu, to_dense, to_halo)
 
-__all__ = ['stem_bn_relu', 'max_pool3s2', 'conv_bn_relu', 'conv_bn_add_relu']
+__all__ = ['stem_bn_relu', 'max_pool3s2', 'conv_bn_relu', 'conv_bn_add_relu', 'set_grouped_path', 'get_grouped_path']
 
 FROZEN_TAIL = ('conv_bn_add_relu: backward through a BatchNorm + add + ReLU tail with frozen statistics (the BatchNorm in eval mode) is out of '
                'scope -- run eval-mode forwards under torch.no_grad(), or keep the BatchNorm layers of a ResNet in training mode')
@@ -137,6 +138,25 @@ GROUPED_CONTRACT = ('conv_bn_relu: a grouped convolution is on this path as a 3x
                     'C = groups * Cg, Cg in {4, 8, 16, 32, 64}, C % 64 == 0 and C <= 2048')
 
 
+# Which kernels a grouped 3x3 takes.  'plain' (the default): the FMA kernels of grouped.hip at every layer, the launches every recorded
+# sequence and every earlier measurement were made with.  'mfma': the matrix-unit kernels of grouped_mfma.hip at the layers they serve (bf16,
+# stride 1); stride 2 and fp32 stay plain.  The default moves only once the measured table of DESIGN 3.12 says it should.
+_GROUPED = {'path': 'plain'}
+
+
+def set_grouped_path(mode):
+    """'plain' | 'mfma' (see above).  Returns the previous mode."""
+    if mode not in ('plain', 'mfma'):
+        raise ValueError("grouped path must be 'plain' or 'mfma'")
+    prev, _GROUPED['path'] = _GROUPED['path'], mode
+    return prev
+
+
+def get_grouped_path():
+    """The path in force for grouped 3x3 layers: 'plain' or 'mfma'."""
+    return _GROUPED['path']
+
+
 def _check_grouped(x, conv):
     Cc, groups = conv.in_channels, conv.groups
     if conv.out_channels != Cc or Cc % groups or Cc // groups not in (4, 8, 16, 32, 64) or Cc % 64 or Cc > 2048 or x.shape[1] != Cc:
@@ -152,7 +172,7 @@ def conv_bn_relu(x, conv, bn, dtype=None):
     if grouped:
         _check_grouped(x, conv)
     training = _check_bn(bn, 'conv_bn_relu')
-    back_end = GroupedConv(conv.groups, stride) if grouped else PlainConv(k, stride)
+    back_end = GroupedConv(conv.groups, stride, _GROUPED['path']) if grouped else PlainConv(k, stride)
     link = _Link() if grad_on and not grouped else None         # the grouped data gradient takes no addend: no link to the block's tail
     z = ConvBNReLUFn.apply(x, conv.weight, None, bn.weight, bn.bias, _BNState(bn), training, dtype or get_compute_dtype(), back_end, link, grad_on)
     if link is not None and link.open:

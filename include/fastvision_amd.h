@@ -817,13 +817,47 @@ int fva_bn_add_relu_bwd_apply(int dtype, const void* dz, const void* y, const fl
  *   unrounded accumulators, in pixel order); fva_bn_finalize takes it unchanged.  NULL: no statistics (eval mode).
  *   fva_gconv_wgrad: workspace of fva_gconv_wgrad_workspace(d) bytes (0 for a descriptor outside the contract); FVA_ERR_WORKSPACE if short.
  * No float atomics, fixed summation order: every launch gives the same bits twice.  fp32 tensors accumulate in double and round once.
- * All three run on plain FMA kernels at both strides (grouped.hip); no MFMA kernel is built. */
+ * All three run on plain FMA kernels at both strides (grouped.hip); the matrix-unit path for bf16 at stride 1 is fva_gconv_mfma_* below. */
 typedef struct { int32_t dtype, B, H, W, C, groups, stride, in_pad, dy_pad; } fva_gconv_desc;   /* 3x3, padding 1, Cin == Cout == C */
 int     fva_gconv_fwd(const fva_gconv_desc*, const void* x, const float* w_oihw, void* y, float* stats_partial, void* stream);
 int32_t fva_gconv_stat_blocks(const fva_gconv_desc*);
 int     fva_gconv_dgrad(const fva_gconv_desc*, const void* dy, const float* w_oihw, void* dx, void* stream);
 int     fva_gconv_wgrad(const fva_gconv_desc*, const void* x, const void* dy, float* dw_oihw, void* workspace, int64_t workspace_bytes, void* stream);
 int64_t fva_gconv_wgrad_workspace(const fva_gconv_desc*);
+
+/* ---- The same convolution on the matrix units (grouped_mfma.hip; version 11) ------------------------------------------------------------
+ * A second path beside fva_gconv_*, for the layers that carry ResNeXt's time: dtype FVA_BF16, stride 1, in_pad == dy_pad == 1, the C / Cg
+ * contract above, B (H + 2)(W + 2) < 2^31, and a map whose staging fits 64 KB of LDS (W <= 70).  fva_gconv_mfma_serves answers 1 / 0 for a
+ * descriptor (pure host, sets no error); every other entry point refuses a descriptor it answers 0 for with FVA_ERR_ARG and a message that
+ * names this contract, and launches nothing (the size functions return 0).  Tensors as above: x / dy halo (border 1, zero), y / dx dense,
+ * dw fp32 [C][Cg][3][3].  The caller chooses the path; nothing falls back.
+ *   fva_gconv_mfma_pack: the fp32 master weight -> two bf16 tables (round to nearest even: the values the plain path multiplies), forward
+ *   and data gradient, fva_gconv_mfma_pack_bytes(d) bytes EACH.  One small launch, meant to run in front of every forward (nothing is
+ *   cached or keyed on the parameter: a captured step replays it on the weights the optimizer has just written).  Table layout
+ *   [C / 16 slabs][steps][64 lanes][8 elements], the A fragments of v_mfma_f32_16x16x32_bf16: lane l, element j is row m = l % 16 (channel
+ *   c = 16 slab + m, whose output the row computes), k = 8 (l / 16) + j.
+ *     Cg >= 32: steps = 9 Cg / 32, step = tap * (Cg / 32) + h, the row's partner channel is kc = 32 h + k of c's group (first channel gb):
+ *               forward w[c][kc][tap], data gradient w[gb + kc][c - gb][8 - tap].
+ *     Cg <= 16: steps = 5, tap = 2 step + k / 16, the partner is channel kc = k % 16 of the slab; zero unless tap < 9 and kc / Cg == m / Cg
+ *               (the block diagonal): forward w[c][kc % Cg][tap], data gradient w[16 slab + kc][m % Cg][8 - tap].
+ *   fva_gconv_mfma_fwd: stats_partial [fva_bn_partial_rows(fva_gconv_mfma_stat_blocks(d))][2][C]: one row per block of 256 consecutive
+ *   PADDED positions (b, yy, xx over [B][H + 2][W + 2]), the sums of y and y^2 over the block's real pixels from the unrounded
+ *   accumulators; fva_bn_finalize takes it unchanged with count = B H W.  NULL: no statistics (eval mode).
+ *   fva_gconv_mfma_wgrad: workspace of fva_gconv_mfma_wgrad_workspace(d) bytes (fp32 partials per run of positions, added in their order by
+ *   a second launch); FVA_ERR_WORKSPACE if short.
+ * Arithmetic: the products of two bf16 values are exact in fp32; they are accumulated in fp32 in a fixed order (no atomics: the same bits
+ * on every run), the statistics in double.  y and dx are rounded to bf16 once.  Cg < 16 multiplies a slab of 16 / Cg groups by a
+ * block-diagonal fragment, so a NON-FINITE input in one group reaches the other groups of its 16-channel slab through zero times infinity
+ * (NaN); the plain path does not do this.  The weight gradient sums over the padded positions: dy's zero border adds exact zeros, and a
+ * non-finite x next to it would not. */
+int     fva_gconv_mfma_serves(const fva_gconv_desc*);
+int64_t fva_gconv_mfma_pack_bytes(const fva_gconv_desc*);
+int     fva_gconv_mfma_pack(const fva_gconv_desc*, const float* w_oihw, void* wpack_fwd, void* wpack_dgrad, void* stream);
+int32_t fva_gconv_mfma_stat_blocks(const fva_gconv_desc*);
+int     fva_gconv_mfma_fwd(const fva_gconv_desc*, const void* x, const void* wpack_fwd, void* y, float* stats_partial, void* stream);
+int     fva_gconv_mfma_dgrad(const fva_gconv_desc*, const void* dy, const void* wpack_dgrad, void* dx, void* stream);
+int64_t fva_gconv_mfma_wgrad_workspace(const fva_gconv_desc*);
+int     fva_gconv_mfma_wgrad(const fva_gconv_desc*, const void* x, const void* dy, float* dw_oihw, void* ws, int64_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

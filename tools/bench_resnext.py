@@ -5,15 +5,18 @@ CrossEntropyLoss, backward, FusedSGD(momentum=0.9, nesterov=True, weight_decay=5
 Per model, on identically seeded weights (wall time over --steps steps after --warmup, device synchronised at both ends):
     eager     the library step
     torch     the same network from stock torch.nn modules on the same GPU (bf16 autocast, channels_last, torch.optim.SGD)
-eager and torch ALTERNATE in one process, --rounds times each after warm-up; the figure per mode is the median of its rounds.
+eager and torch ALTERNATE in one process, --rounds times each after warm-up; the figure per mode is the median of its rounds.  The eager
+step is taken once per grouped path of --grouped (resnet_ops.set_grouped_path: 'plain', the FMA kernels of csrc/grouped.hip, and 'mfma',
+the matrix-unit kernels of csrc/grouped_mfma.hip at the stride-1 layers), all in the same alternation; every figure carries a ``grouped`` key.
 
-Per grouped kernel (fva_gconv_fwd with statistics, fva_gconv_dgrad, fva_gconv_wgrad) at the six stride-1 shapes of DESIGN 3.12: device-event
-time over --iters launches after warm-up, the bytes of x read + y written once (the floor's bytes), the useful GFLOP, and a
-device-to-device copy of the same number of bytes measured right beside it.
+Per grouped kernel (forward with statistics, data gradient, weight gradient; under 'mfma' also the pack launch that precedes every forward)
+at the six stride-1 shapes of DESIGN 3.12 and per path: device-event time over --iters launches after warm-up, the paths and a
+device-to-device copy of x read + y written once (the floor's bytes) ALTERNATING --rounds times in one process; per figure the median, the
+best, and the spread between its rounds, the useful GFLOP, and under 'mfma' whether every round beat every round of 'plain'.
 
 Writes one JSON object to --out (default profiles/bench_resnext.json) and prints it as one line.
 usage: python tools/bench_resnext.py [--steps K] [--warmup W] [--batch B] [--size S] [--rounds R] [--iters N] [--models a,b] [--modes eager,torch]
-[--no-kernels] [--out PATH]"""
+[--grouped plain,mfma] [--no-kernels] [--out PATH]"""
 import argparse
 import ctypes as C
 import json
@@ -22,14 +25,14 @@ import statistics
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from bench_resnet import DEV, NUM_CLASSES, SGD_KW, timed, with_copy          # noqa: E402  (puts the repository root on the path too)
+from bench_resnet import DEV, NUM_CLASSES, SGD_KW, event_us, timed          # noqa: E402  (puts the repository root on the path too)
 
 import torch          # noqa: E402
 import torch.nn as nn          # noqa: E402
 import torch.nn.functional as F          # noqa: E402
 
 import fastvision_amd          # noqa: E402
-from fastvision_amd import FusedSGD, _lib, ops          # noqa: E402
+from fastvision_amd import FusedSGD, _lib, ops, resnet_ops          # noqa: E402
 from fastvision_amd.classfication import models          # noqa: E402
 from fastvision_amd.loss import CrossEntropyLoss          # noqa: E402
 
@@ -76,6 +79,7 @@ class TorchResNeXt(nn.Module):
 
 
 def make_step(name, mode, images, labels):
+    """``mode``: 'torch', or 'eager/<grouped path>'"""
     torch.manual_seed(0)
     if mode == 'torch':
         net = TorchResNeXt(name).to(DEV).to(memory_format=torch.channels_last).train()
@@ -94,8 +98,14 @@ def make_step(name, mode, images, labels):
     opt = FusedSGD(net.parameters(), capturable=True, **SGD_KW)
     crit = CrossEntropyLoss()
 
+    grouped = mode.split('/')[1]
+
     def step():
-        pred = net(images)
+        prev = resnet_ops.set_grouped_path(grouped)         # read at call time by every grouped layer of the forward
+        try:
+            pred = net(images)
+        finally:
+            resnet_ops.set_grouped_path(prev)
         opt.zero_grad(set_to_none=True)
         loss = crit(pred, labels)
         loss.backward()
@@ -104,10 +114,14 @@ def make_step(name, mode, images, labels):
     return step
 
 
+def _modes(args):
+    return [f'eager/{g}' for m in args.modes.split(',') if m == 'eager' for g in args.grouped.split(',')] + [m for m in args.modes.split(',') if m != 'eager']
+
+
 def bench_models(args, images, labels):
     out = {}
     for name in args.models.split(','):
-        steps = {m: make_step(name, m, images, labels) for m in args.modes.split(',')}
+        steps = {m: make_step(name, m, images, labels) for m in _modes(args)}
         for st in steps.values():
             for _ in range(args.warmup):
                 st()
@@ -118,40 +132,80 @@ def bench_models(args, images, labels):
                 ms, last[m] = timed(st, args.steps)
                 runs[m].append(ms)
         out[name] = {m: {'ms_per_step': round(statistics.median(v), 3), 'img_per_s': round(args.batch / statistics.median(v) * 1e3, 1),
-                         'spread': round((max(v) - min(v)) / statistics.median(v), 4), 'last_loss': round(last[m], 5)} for m, v in runs.items()}
+                         'spread': round((max(v) - min(v)) / statistics.median(v), 4), 'last_loss': round(last[m], 5),
+                         'grouped': m.split('/')[1] if '/' in m else None} for m, v in runs.items()}
         del steps
         torch.cuda.empty_cache()
     return out
+
+
+ENTRY = {'plain': ('fva_gconv_fwd', 'fva_gconv_dgrad', 'fva_gconv_wgrad', 'fva_gconv_stat_blocks', 'fva_gconv_wgrad_workspace'),
+         'mfma': ('fva_gconv_mfma_fwd', 'fva_gconv_mfma_dgrad', 'fva_gconv_mfma_wgrad', 'fva_gconv_mfma_stat_blocks', 'fva_gconv_mfma_wgrad_workspace')}
+
+
+def _halo_randn(B, H, Cc, dt):
+    t = torch.zeros(B, H + 2, H + 2, Cc, dtype=dt, device=DEV)
+    t[:, 1:-1, 1:-1] = torch.randn(B, H, H, Cc, device=DEV).to(dt)
+    return t
 
 
 def bench_kernels(args):
     dt, code, p, st = torch.bfloat16, _lib.BF16, ops._p, ops._stream
     lib = _lib.load()
     B, it, E = args.batch, args.iters, 2
+    paths = args.grouped.split(',')
     rows = []
     for tag, Cc, Cg, H in SHAPES:
         H = H * args.size // 224
         d = _lib.GConvDesc(code, B, H, H, Cc, Cc // Cg, 1, 1, 1)
         M = B * H * H
-        x = torch.randn(B, H + 2, H + 2, Cc, device=DEV).to(dt)
-        dy = torch.randn(B, H + 2, H + 2, Cc, device=DEV).to(dt)
+        x, dy = _halo_randn(B, H, Cc, dt), _halo_randn(B, H, Cc, dt)
         w = torch.randn(Cc, Cg, 3, 3, device=DEV) * (9 * Cg) ** -0.5
         y = torch.empty((M, Cc), dtype=dt, device=DEV)
         dx = torch.empty((B, H, H, Cc), dtype=dt, device=DEV)
         dw = torch.empty((Cc, Cg, 3, 3), dtype=torch.float32, device=DEV)
-        nblk = lib.fva_gconv_stat_blocks(C.byref(d))
-        stats = torch.empty((lib.fva_bn_partial_rows(nblk), 2, Cc), dtype=torch.float32, device=DEV)
-        wsb = lib.fva_gconv_wgrad_workspace(C.byref(d))
-        ws = torch.empty(wsb, dtype=torch.uint8, device=DEV)
         nbytes, gflop = 2 * M * Cc * E, 2.0 * M * Cc * Cg * 9 / 1e9
-        for name, fn in (('fva_gconv_fwd', lambda: _lib.call('fva_gconv_fwd', C.byref(d), p(x), p(w), p(y), p(stats), st())),
-                         ('fva_gconv_dgrad', lambda: _lib.call('fva_gconv_dgrad', C.byref(d), p(dy), p(w), p(dx), st())),
-                         ('fva_gconv_wgrad', lambda: _lib.call('fva_gconv_wgrad', C.byref(d), p(x), p(dy), p(dw), p(ws), wsb, st()))):
-            r = with_copy(name, fn, nbytes, it, (B, H, H, Cc))
-            r.update({'layer': tag, 'Cg': Cg, 'useful_gflop': round(gflop, 2), 'useful_tflop_per_s': round(gflop / r['us'] * 1e3, 2),
-                      'hbm_floor_us_at_5p5_tb_per_s': round(nbytes / 5.5e6, 1)})
+        src = torch.empty(nbytes // 2, dtype=torch.uint8, device=DEV)
+        dst = torch.empty_like(src)
+        fns, keep = {}, []
+        for g in paths:
+            if g == 'mfma' and lib.fva_gconv_mfma_serves(C.byref(d)) != 1:
+                continue
+            fwd, dgrad, wgrad, blocks, wsf = ENTRY[g]
+            nblk = getattr(lib, blocks)(C.byref(d))
+            stats = torch.empty((lib.fva_bn_partial_rows(nblk), 2, Cc), dtype=torch.float32, device=DEV)
+            wsb = getattr(lib, wsf)(C.byref(d))
+            ws = torch.empty(wsb, dtype=torch.uint8, device=DEV)
+            wf = wb = w
+            if g == 'mfma':
+                nb = lib.fva_gconv_mfma_pack_bytes(C.byref(d))
+                wf, wb = torch.empty(nb, dtype=torch.uint8, device=DEV), torch.empty(nb, dtype=torch.uint8, device=DEV)
+                fns[(g, 'fva_gconv_mfma_pack')] = lambda wf=wf, wb=wb: _lib.call('fva_gconv_mfma_pack', C.byref(d), p(w), p(wf), p(wb), st())
+                fns[(g, 'fva_gconv_mfma_pack')]()
+            keep.append((stats, ws, wf, wb))
+            fns[(g, fwd)] = lambda fwd=fwd, wf=wf, stats=stats: _lib.call(fwd, C.byref(d), p(x), p(wf), p(y), p(stats), st())
+            fns[(g, dgrad)] = lambda dgrad=dgrad, wb=wb: _lib.call(dgrad, C.byref(d), p(dy), p(wb), p(dx), st())
+            fns[(g, wgrad)] = lambda wgrad=wgrad, ws=ws, wsb=wsb: _lib.call(wgrad, C.byref(d), p(x), p(dy), p(dw), p(ws), wsb, st())
+        us = {k: [] for k in fns}
+        copy_us = []
+        for _ in range(args.rounds):                        # the paths and the copy alternate: one round = every figure once
+            for k, fn in fns.items():
+                us[k].append(event_us(fn, it))
+            copy_us.append(event_us(lambda: dst.copy_(src), it))
+        cu = min(copy_us)
+        for (g, name), v in us.items():
+            med = statistics.median(v)
+            r = {'kernel': name, 'grouped': g, 'layer': tag, 'Cg': Cg, 'shape': [B, H, H, Cc], 'bytes': nbytes, 'us': round(med, 1),
+                 'us_best': round(min(v), 1), 'us_rounds': [round(t, 1) for t in v], 'spread': round((max(v) - min(v)) / med, 4),
+                 'gb_per_s': round(nbytes / med / 1e3, 1), 'copy_us': round(cu, 1), 'copy_gb_per_s': round(nbytes / cu / 1e3, 1),
+                 'share_of_copy_rate': round(cu / med, 3), 'useful_gflop': round(gflop, 2), 'useful_tflop_per_s': round(gflop / med * 1e3, 2),
+                 'hbm_floor_us_at_5p5_tb_per_s': round(nbytes / 5.5e6, 1)}
+            twin = ENTRY['plain'][ENTRY['mfma'].index(name)] if g == 'mfma' and name in ENTRY['mfma'] else None
+            if twin is not None and ('plain', twin) in us:
+                r['plain_us'] = round(statistics.median(us[('plain', twin)]), 1)
+                r['beats_plain_in_every_round'] = max(v) < min(us[('plain', twin)])      # by more than the spread between rounds of a mode
             rows.append(r)
-        del x, dy, y, dx, ws
+        del x, dy, y, dx, keep, fns
     return rows
 
 
@@ -165,6 +219,7 @@ def main():
     ap.add_argument('--size', type=int, default=224)
     ap.add_argument('--models', default='resnext50_32x4d,resnext101_32x8d')
     ap.add_argument('--modes', default='eager,torch')
+    ap.add_argument('--grouped', default='plain,mfma')
     ap.add_argument('--no-kernels', action='store_true')
     ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'bench_resnext.json'))
     args = ap.parse_args()
@@ -176,12 +231,16 @@ def main():
     out = {'workload': f'ResNeXt classification train step B={args.batch} 3x{args.size}x{args.size} {NUM_CLASSES} classes bf16, SGD nesterov',
            'steps': args.steps, 'warmup': args.warmup, 'rounds': args.rounds, 'device': torch.cuda.get_device_name(0),
            'reference': 'torch: the same network from stock torch.nn on the same device, bf16 autocast, channels_last, torch.optim.SGD',
-           'grouped_kernels': 'the plain FMA path of csrc/grouped.hip (no MFMA kernel is built)'}
+           'grouped_paths': {'plain': 'the FMA kernels of csrc/grouped.hip at every grouped layer (the default of resnet_ops)',
+                             'mfma': 'the matrix-unit kernels of csrc/grouped_mfma.hip at the bf16 stride-1 layers, plain elsewhere'}}
+    for g in args.grouped.split(','):
+        if g not in ENTRY:
+            raise SystemExit(f'bench_resnext: --grouped takes plain and mfma, got {g}')
     with fastvision_amd.compute_dtype(torch.bfloat16):
         out.update(bench_models(args, images, labels))
         if not args.no_kernels:
             out['kernels'] = bench_kernels(args)
-            out['kernels_measured_against'] = 'a device-to-device copy of x read + y written (the same number of bytes), same process'
+            out['kernels_measured_against'] = 'a device-to-device copy of x read + y written (the same number of bytes), same process, alternating with the kernels'
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, 'w') as f:
         json.dump(out, f, indent=1)
