@@ -104,6 +104,11 @@ class MatchOut(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ('count', 'b', 'gx', 'gy', 'a', 'cls', 'xywh', 'anc')]
 
 
+class MixPlan(C.Structure):
+    """fva_mix_plan_t: what fva_mix_plan decided for one batch (nine 32-bit words; it lives in device memory as an int32[9] tensor)"""
+    _fields_ = [('mode', C.c_int32), ('lam_raw', C.c_float), ('lam', C.c_float)] + [(n, C.c_int32) for n in ('rx', 'ry', 'x1', 'y1', 'x2', 'y2')]
+
+
 _P, _I, _L, _F = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 _D = C.POINTER(ConvDesc)
 _H = C.POINTER(HeadLevel)
@@ -257,6 +262,10 @@ PROTOTYPES = {
     'fva_gconv_mfma_dgrad': (_I, [_G, _P, _P, _P, _P]),
     'fva_gconv_mfma_wgrad_workspace': (_L, [_G]),
     'fva_gconv_mfma_wgrad': (_I, [_G, _P, _P, _P, _P, _L, _P]),
+    'fva_mix_plan': (_I, [_P, _F, _F, _F, _F, _I, _I, _P, _P]),
+    'fva_mix_apply': (_I, [_I, _P, _P, _P, _I, _I, _I, _I, _P]),
+    'fva_softmax_ce_soft': (_I, [_P, _P, _I, _P, _P, _I, _I, _I, _F, _P, _P, _P, _P, _P]),
+    'fva_topk_accuracy': (_I, [_P, _I, _P, _I, _I, _I, _I, _P, _P, _P]),
 }
 LABEL_I64, LABEL_F32 = 0, 1
 REDUCE_MEAN, REDUCE_SUM = 0, 1

@@ -1,7 +1,7 @@
 #include "common.h"
 thread_local char fva_err_buf[512] = "";
 extern "C" const char* fva_last_error(void) { return fva_err_buf; }
-extern "C" int fva_version(void) { return 11; }
+extern "C" int fva_version(void) { return 12; }
 static thread_local const char* g_last_kernel = "";
 void fva_note_kernel(const char* name) { g_last_kernel = name; }
 extern "C" const char* fva_conv_last_kernel(void) { return g_last_kernel; }

@@ -85,6 +85,8 @@ class GraphedTrainStep:
     ``ema`` (ModelEMA, optional): ``ema.update(model)`` follows the optimizer step inside the captured sequence -- its update counter and
     weight live on the device, so each replay applies the next point of the ramp; warm-up and capture leave the average and its
     counter untouched, and after each replay the versions of the averaged model's tensors are advanced.
+    ``mix`` (BatchMix, optional): ``images, targets = mix(images, targets)`` runs inside the captured sequence in front of the forward
+    pass -- its seed and call counter live on the device, so each replay draws a new plan; warm-up and capture leave its state untouched.
 
         step = GraphedTrainStep(model, lambda pred, tg: criterion(pred, tg), optimizer, images, targets, max_targets=1280)
         for images, targets in loader:
@@ -92,13 +94,14 @@ class GraphedTrainStep:
     """
 
     def __init__(self, model, loss_fn, optimizer, images, targets, max_targets=None, warmup=2, pre_step=None, on_capture=None,
-                 side_stream=False, ema=None):
+                 side_stream=False, ema=None, mix=None):
         if not getattr(optimizer, 'capturable', False):
             raise RuntimeError('GraphedTrainStep needs FusedAdam(..., capturable=True) or FusedSGD(..., capturable=True): '
                                'step count and LR must live on the device')
         if not model.training:
             raise RuntimeError('GraphedTrainStep: put the model in train mode first')
         self.model, self.loss_fn, self.optimizer, self.pre_step, self.ema = model, loss_fn, optimizer, pre_step, ema
+        self.mix = mix
         self.params = [p for g in optimizer.param_groups for p in g['params']]
         T = int(targets.shape[0])
         self.capacity = int(max_targets) if max_targets is not None else T
@@ -152,9 +155,12 @@ class GraphedTrainStep:
         self.replays = 0
 
     def _step(self):
-        pred = self.model(self.images)
+        images, targets = self.images, self.targets
+        if self.mix is not None:
+            images, targets = self.mix(images, targets)
+        pred = self.model(images)
         self.optimizer.zero_grad(set_to_none=True)
-        loss = self.loss_fn(pred, self.targets)
+        loss = self.loss_fn(pred, targets)
         loss.backward()
         if self.pre_step is not None:
             self.pre_step()
@@ -167,12 +173,16 @@ class GraphedTrainStep:
         snap = snapshot_train_state(self.model, self.optimizer)
         if self.ema is not None:
             snap['ema'] = self.ema.snapshot_state()
+        if self.mix is not None:
+            snap['mix'] = self.mix.snapshot_state()
         return snap
 
     def _restore(self, snap):
         restore_train_state(self.model, self.optimizer, snap)
         if self.ema is not None:
             self.ema.restore_state(snap['ema'])
+        if self.mix is not None:
+            self.mix.restore_state(snap['mix'])
 
     def __call__(self, images=None, targets=None):
         if images is not None:

@@ -9,6 +9,9 @@ candidate counts), the losses and the mAP rows are read back once at the end.
 
 ``ema=`` (fastvision_amd.ModelEMA, not in the reference): updated after every optimizer step; ``_val`` then evaluates the averaged model
 (forward and loss) and the per-epoch checkpoint gains an ``'ema'`` entry.  Without it the loop is the reference's.
+
+``mix=`` (fastvision_amd.BatchMix, not in the reference): ``images, labels = mix(images, labels)`` in ``_train`` once the batch is on
+the device -- the loss then receives ``MixedLabels`` (loss.CrossEntropyLoss takes them).  ``_val`` never mixes.
 """
 import numpy as np
 import torch
@@ -56,7 +59,17 @@ class stall_watch:
             faulthandler.cancel_dump_traceback_later()
 
 
-class Fit:
+class _FitCall(type):
+    """``Fit(..., mix=None)``: the keyword is taken off by the class call and stored on the instance.  ``Fit.__init__`` keeps the
+    argument list it has had since ``ema`` was added -- callers and tests/test_ema_cpu.py rely on that list as it stands."""
+
+    def __call__(cls, *args, mix=None, **kwargs):
+        self = super().__call__(*args, **kwargs)
+        self.mix = mix                              # BatchMix: MixUp / CutMix of every training batch, drawn and applied on the device
+        return self
+
+
+class Fit(metaclass=_FitCall):
     def __init__(self, model, device, optimizer, scheduler, loss, end_epoch, start_epoch=0, train_loader=None, val_loader=None,
                  test_loader=None, data_dict=None, log_every=0, save_last='last.pth', ema=None):
         self.model, self.device, self.optimizer, self.scheduler, self.loss = model, device, optimizer, scheduler, loss
@@ -94,6 +107,8 @@ class Fit:
         for batch_idx, (images, labels) in enumerate(self.train_loader):
             images, labels = self._to_device(images, labels)
             with stall_watch():
+                if self.mix is not None:
+                    images, labels = self.mix(images, labels)
                 pred = self.model(images)
                 self.optimizer.zero_grad()
                 loss = self.loss(pred, labels)

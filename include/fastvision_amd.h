@@ -859,6 +859,60 @@ int     fva_gconv_mfma_dgrad(const fva_gconv_desc*, const void* dy, const void* 
 int64_t fva_gconv_mfma_wgrad_workspace(const fva_gconv_desc*);
 int     fva_gconv_mfma_wgrad(const fva_gconv_desc*, const void* x, const void* dy, float* dw_oihw, void* ws, int64_t ws_bytes, void* stream);
 
+/* ---- Label smoothing, MixUp and CutMix (not in the reference: the standard recipe of its classifiers; version 12) -------------------
+ * fva_mix_plan: a ONE-THREAD tick kernel that decides, on the device, what the next batch gets.  state = int64[4] in DEVICE memory,
+ * {seed, call counter, 0, 0} (the protocol of fva_dropout_fwd): the launch reads seed and counter and advances the counter itself, so a
+ * captured graph draws a new plan on every replay and the host never reads anything back.  All launches that share one state must be
+ * on ONE stream.  Random words: Philox-4x32-10 keyed by the seed's two halves; block j = philox(counter = (j, 0, call counter lo, hi)),
+ * word i of the tick = word i % 4 of block i / 4.  A uniform is u(word) = ((word >> 8) + 0.5f) * 2^-24 in fp32 arithmetic: exact for
+ * word >> 8 < 2^23, the sum rounded to even above (fp32 has no half there), so u lies in (0, 1] and is never 0.
+ *   word 0   apply at all iff u < prob
+ *   word 1   CutMix iff (mixup_alpha > 0 and cutmix_alpha > 0 and u < switch_prob) or (only cutmix_alpha > 0); MixUp iff not CutMix and
+ *            mixup_alpha > 0; both alphas 0: mode 0
+ *   word 2   rx = (uint64(word) * W) >> 32        word 3   ry = (uint64(word) * H) >> 32          (exact integer arithmetic)
+ *   words 4 + 2 i, 5 + 2 i (i = 0, 1, ...)   the i-th pair (U, V) of Johnk's method for lam_raw ~ Beta(alpha, alpha), alpha = the chosen
+ *            mode's: X = U^(1/alpha), Y = V^(1/alpha); accept the first pair with X + Y <= 1 and return X / (X + Y); when X + Y == 0
+ *            (underflow) the log-space form lx = log(U) / alpha, ly = log(V) / alpha, each minus their maximum, exp(lx - log(exp(lx) +
+ *            exp(ly))) -- what numpy's RandomState.beta runs for a, b <= 1.  Evaluated in double from the fp32 uniforms and rounded ONCE
+ *            to fp32.  After 512 rejected pairs (probability below 2^-512) lam_raw = 0.5.
+ * Words 0 ... 3 are always consumed; a tick that does not apply draws no pair.  0 <= alpha <= 1 (alpha > 1: FVA_ERR_ARG), prob and
+ * switch_prob in [0, 1], H, W >= 1 with H * W < 2^31.
+ * The plan: mode (0 none, 1 MixUp, 2 CutMix), lam_raw, lam and, for CutMix, torchvision's box: r = 0.5f * sqrtf(1 - lam_raw),
+ * hw = (int)(r * W), hh = (int)(r * H) (fp32), x1 = max(rx - hw, 0), x2 = min(rx + hw, W), y1, y2 likewise,
+ * lam = 1.f - (float)((x2 - x1) * (y2 - y1)) / (float)(W * H).  MixUp: lam = lam_raw, no box (zeros).  Mode 0: lam = lam_raw = 1.
+ *
+ * fva_mix_apply: out of place over planar [B][C][H][W] of dtype (FVA_F32 / FVA_BF16); the plan is read on the device.  The partner of
+ * image b is (b - 1 + B) % B (batch.roll(1, 0)).  Mode 1: out = fmaf(lam, x_b, (1 - lam) * x_partner) in fp32, rounded once to dtype;
+ * mode 2: the partner's pixel inside [y1, y2) x [x1, x2), a bit-exact copy elsewhere; mode 0, and B == 1 in every mode: a bit-exact
+ * copy.  16-byte accesses when C * H * W and W are multiples of the 16-byte chunk and both pointers are 16-byte aligned, one element
+ * per thread otherwise; 64-bit element offsets.  B <= 65535.
+ *
+ * fva_softmax_ce_soft: fva_softmax_ce with the target q = (1 - smoothing) * t + smoothing / C, where t is
+ *   (a) onehot(y_r)                                              plan == NULL, dense == NULL
+ *   (b) lam * onehot(y_r) + (1 - lam) * onehot(y_((r-1+R) % R))  plan != NULL: lam is read from the plan on the device
+ *   (c) dense[r][:], fp32 [R][C] (torch's probability targets)   dense != NULL (labels ignored; with a plan: FVA_ERR_ARG)
+ * row loss = w_r * (sum(q) * lse - sum_k q_k z_k) = -w_r * sum_k q_k log_softmax(z)_k (sum(q) = 1 for (a) and (b), so lse - sum q z),
+ * grad = scale * w_r * (softmax * sum(q) - q); reduction, weights, workspace (fva_softmax_ce_workspace) and the fixed-order double sum
+ * as fva_softmax_ce.  An invalid label makes every row that uses it NaN and no other: row r and, under (b), row r + 1; no memory is
+ * indexed with it.  smoothing in [0, 1].  With smoothing == 0 and form (a), value and gradient equal fva_softmax_ce bit for bit.
+ *
+ * fva_topk_accuracy: out[0] = (rows with #{j : z_j beats z_y} < k) / R; "beats" is the order of fva_top1_accuracy's argmax (a NaN is
+ * largest, among equals the smaller index wins), so k = 1 equals fva_top1_accuracy exactly; k >= 1; a label out of range (or not an
+ * integer) never hits.  workspace: R int32. */
+typedef struct {
+    int32_t mode;              /* 0 none, 1 MixUp, 2 CutMix */
+    float lam_raw, lam;
+    int32_t rx, ry, x1, y1, x2, y2;
+} fva_mix_plan_t;
+int fva_mix_plan(int64_t* state, float mixup_alpha, float cutmix_alpha, float prob, float switch_prob, int32_t H, int32_t W,
+                 fva_mix_plan_t* plan, void* stream);
+int fva_mix_apply(int dtype, const void* x, void* out, const fva_mix_plan_t* plan, int32_t B, int32_t C, int32_t H, int32_t W, void* stream);
+int fva_softmax_ce_soft(const float* logits, const void* labels, int label_dtype, const float* dense, const float* weights, int32_t R,
+                        int32_t C, int32_t reduction, float smoothing, const fva_mix_plan_t* plan, float* loss_out, float* grad,
+                        void* workspace, void* stream);
+int fva_topk_accuracy(const void* logits, int logits_dtype, const void* labels, int label_dtype, int32_t R, int32_t C, int32_t k, float* out,
+                      void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
