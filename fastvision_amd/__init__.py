@@ -17,7 +17,7 @@ runs in hand-written HIP kernels behind the C ABI of include/fastvision_amd.h (c
 is cheap, the shared library is loaded on first use and its absence is an error (no CPU fallback).
 """
 from .ops import compute_dtype, get_compute_dtype, set_compute_dtype  # noqa: F401
-from .optim import FusedAdam, FusedSGD  # noqa: F401
+from .optim import FusedAdam, FusedLAMB, FusedLARS, FusedSGD, layerwise_groups  # noqa: F401
 from .ema import ModelEMA  # noqa: F401
 from .mix import BatchMix, MixedLabels  # noqa: F401
 

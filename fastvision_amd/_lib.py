@@ -195,6 +195,8 @@ PROTOTYPES = {
     'fva_sgd_chunk_elems': (_I, []),
     'fva_sgd_clip_coef': (_I, [_P, _I, _P, _I, _P, C.c_double, _P, _P]),
     'fva_sgd_step': (_I, [_P, _I, _P, _I, _P, _P, _I, _P, _P]),
+    'fva_lars_step': (_I, [_P, _I, _P, _I, _P, _P, _P, _I, C.c_double, _P, _P, _P, _P]),
+    'fva_lamb_step': (_I, [_P, _I, _P, _I, _P, _P, _I, _P, C.c_double, _P, _P, _P, _P]),
     'fva_ema_chunk_elems': (_I, []),
     'fva_ema_update': (_I, [_P, _I, _P, _I, C.c_double, C.c_double, _P, _P]),
     'fva_paste_resize_normalize': (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),

@@ -18,7 +18,7 @@ from . import _lib
 from .multi_tensor import WordTable, capturing, chunk_words, chunks_of, upload_words
 from .ops import _stream, join_side_stream
 
-__all__ = ['FusedAdam', 'FusedSGD']
+__all__ = ['FusedAdam', 'FusedSGD', 'FusedLARS', 'FusedLAMB', 'layerwise_groups']
 
 
 class _FusedOptimizer(torch.optim.Optimizer):
@@ -393,4 +393,246 @@ class FusedSGD(_FusedOptimizer):
             coef = C.c_void_p(self._clip_out.data_ptr() + 4)
         _lib.call('fva_sgd_step', tab, n, chunks, nchunks, C.c_void_p(self._hyper[1].data_ptr()), C.c_void_p(self._fresh.data_ptr()),
                   1 if clear else 0, coef, _stream())
+        return ps
+
+
+# ---- layer-wise trust ratios: LARS on FusedSGD, LAMB on FusedAdam ---------------------------------------------------------------
+def layerwise_groups(model, weight_decay):
+    """The usual two parameter groups of a large-batch recipe, for ``FusedLARS`` or ``FusedLAMB`` alike: matrices and filters
+    (``ndim > 1``) get weight decay and the trust ratio, biases and normalisation parameters (``ndim <= 1``) get neither."""
+    ps = [p for p in model.parameters() if p.requires_grad]
+    groups = [{'params': [p for p in ps if p.ndim > 1], 'weight_decay': weight_decay},
+              {'params': [p for p in ps if p.ndim <= 1], 'weight_decay': 0.0, 'trust_coefficient': 0.0, 'trust': False}]
+    return [g for g in groups if g['params']]
+
+
+def _refresh_hyper(name, hyper, vals, dev):
+    """(host values, device double table) of the groups' hyper-parameters: uploaded when they changed, into the same device tensor
+    while its size holds (captured steps read that address)."""
+    if hyper is not None and hyper[0] == vals:
+        return hyper
+    if capturing(dev):
+        raise RuntimeError(f'{name}: hyper-parameters changed during a graph capture; call sync_lr() before capturing')
+    same = hyper is not None and hyper[1].numel() == len(vals)
+    return vals, upload_words(vals, dev, torch.float64, out=hyper[1] if same else None)[1]
+
+
+def _clip_value(clip_norm):
+    if clip_norm is not None and not (0.0 < float(clip_norm) < float('inf')):
+        raise ValueError(f'Invalid clip_norm value: {clip_norm}')
+    return None if clip_norm is None else float(clip_norm)
+
+
+class _TrustWorkspace:
+    """What the trust pass needs beside the chunk table, rebuilt when the tensor sizes change: ``first`` (int64 [n + 1], the index of
+    every tensor's first chunk, then the chunk count), ``partial`` (double [2][nchunks]) and ``ratio`` (float [n])."""
+
+    def __init__(self, name):
+        self._first = WordTable(f'{name}: run at least one eager step() before capturing a graph')
+        self.partial = self.ratio = None
+
+    def first(self, sizes, dev):
+        def words():
+            per = _lib.call('fva_sgd_chunk_elems')
+            first = [0]
+            for s in sizes:
+                first.append(first[-1] + chunks_of(s, per))
+            self.partial = torch.empty(2 * first[-1], dtype=torch.float64, device=dev)
+            self.ratio = torch.ones(len(sizes), dtype=torch.float32, device=dev)
+            return first
+
+        return self._first.get(sizes, words, dev)
+
+
+def _ptr(t):
+    return C.c_void_p(t.data_ptr() if t is not None else 0)
+
+
+class FusedLARS(FusedSGD):
+    """Layer-wise adaptive rate scaling on ``FusedSGD``'s update, every group in the same three launches (``fva_lars_step``: norm
+    pass, trust pass, apply pass).  Per tensor, with ``g = c * grad`` (``c``: the clip coefficient, 1 without ``clip_norm``)::
+
+        q = trust_coefficient * |p| / (|g| + weight_decay * |p| + eps)   if trust_coefficient, |p|, |g| > 0, else 1
+        g = q * (g + weight_decay * p);  then SGD's momentum buffer, Nesterov and  p -= lr * g
+
+    A group with ``trust_coefficient=0`` (biases, BatchNorm: ``layerwise_groups``) takes plain SGD.  The norms are fp64 in a fixed
+    order, the ratio is stored as fp32 (``last_trust_ratio``: one entry per parameter that had a gradient, in group order).  Every
+    other argument, check, the state layout, checkpoints, ``clip_norm`` / ``last_grad_norm`` and ``capturable`` are ``FusedSGD``'s; the
+    clipping norm comes out of the norm pass, at no extra pass over the gradients.  A checkpoint of ``torch.optim.SGD`` has no
+    ``trust_coefficient`` / ``eps``: loading one keeps each group's present values."""
+
+    def __init__(self, params, lr=1e-3, momentum=0, dampening=0, weight_decay=0, nesterov=False, trust_coefficient=0.001, eps=1e-8,
+                 clip_norm=None, capturable=False, **torch_options):
+        if trust_coefficient < 0.0:
+            raise ValueError(f'Invalid trust_coefficient value: {trust_coefficient}')
+        if eps < 0.0:
+            raise ValueError(f'Invalid eps value: {eps}')
+        self._extra = dict(trust_coefficient=trust_coefficient, eps=eps)
+        super().__init__(params, lr, momentum, dampening, weight_decay, nesterov, clip_norm, capturable, **torch_options)
+        self.defaults.update(self._extra)
+        self._tab.capture_error = self._tab.capture_error.replace('FusedSGD', 'FusedLARS')
+        self._work = _TrustWorkspace('FusedLARS')
+
+    def add_param_group(self, group):
+        super().add_param_group(group)
+        for k, v in self._extra.items():
+            self.param_groups[-1].setdefault(k, v)
+
+    def load_state_dict(self, state_dict):
+        kept = [{k: g[k] for k in self._extra} for g in self.param_groups]
+        super().load_state_dict(state_dict)
+        for g, old in zip(self.param_groups, kept):
+            for k, v in old.items():
+                g.setdefault(k, v)
+
+    @property
+    def last_trust_ratio(self):
+        return self._work.ratio
+
+    def _sync_hyper(self, dev):
+        vals = tuple(float(v) for g in self.param_groups for v in (g['lr'], g['weight_decay'], g['momentum'], 1.0 - float(g['dampening']),
+                                                                   1.0 if g['nesterov'] else 0.0, g['trust_coefficient'], g['eps']))
+        self._hyper = _refresh_hyper('FusedLARS', self._hyper, vals, dev)
+
+    def _launch(self):
+        got = self._table()
+        if got is None:
+            return []
+        ps, tab, n, chunks, clear = got
+        dev = ps[0].device
+        self._sync_hyper(dev)
+        first = self._work.first(tuple(p.numel() for p in ps), dev)
+        if self.clip_norm is not None and self._clip_out is None:
+            if capturing(dev):
+                raise RuntimeError('FusedLARS: run at least one eager step() before capturing a graph')
+            self._clip_out = torch.zeros(2, dtype=torch.float32, device=dev)
+        _lib.call('fva_lars_step', _ptr(tab), n, _ptr(chunks), chunks.numel(), _ptr(first), _ptr(self._hyper[1]), _ptr(self._fresh),
+                  1 if clear else 0, self.clip_norm or 0.0, _ptr(self._work.partial), _ptr(self._work.ratio), _ptr(self._clip_out), _stream())
+        return ps
+
+
+class FusedLAMB(FusedAdam):
+    """LAMB: Adam's moments with a layer-wise trust ratio, every group in the same launches (``fva_lamb_step``: tick, norm pass,
+    trust pass, apply pass).  Per tensor, with ``g = c * grad`` and the step count ``t`` starting at 1::
+
+        m = beta1 * m + (1 - beta1) * g;  v = beta2 * v + (1 - beta2) * g * g
+        u = (m / (1 - beta1^t)) / (sqrt(v / (1 - beta2^t)) + eps) + weight_decay * p
+        r = |p| / |u|   if trust and |p|, |u| > 0, else 1;   p -= lr * r * u
+
+    The state is ``FusedAdam``'s (``step``, ``exp_avg``, ``exp_avg_sq``): checkpoints move between the two (a ``FusedAdam`` checkpoint
+    has no ``trust``: loading one keeps each group's present value).  One step count serves all parameters; it and the bias corrections
+    are ticked on the device, so a captured step replays correctly.  ``clip_norm`` / ``last_grad_norm`` as ``FusedSGD``: the global
+    norm is taken first (``grad_sqnorm_partial`` + ``clip_coef``), ``p.grad`` is not rewritten, nothing is read back.  The norms are
+    fp64 in a fixed order; ``last_trust_ratio`` holds one fp32 entry per parameter that had a gradient, in group order.
+    ``capturable=True`` serves graphs.GraphedTrainStep as ``FusedSGD`` does.  Contiguous fp32 parameters and gradients on the GPU only."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.0, trust=True, clip_norm=None, capturable=False):
+        if lr < 0.0:
+            raise ValueError(f'Invalid learning rate: {lr}')
+        if eps < 0.0:
+            raise ValueError(f'Invalid epsilon value: {eps}')
+        for i, b in enumerate(betas):
+            if not 0.0 <= b < 1.0:
+                raise ValueError(f'Invalid beta parameter at index {i}: {b}')
+        if weight_decay < 0.0:
+            raise ValueError(f'Invalid weight_decay value: {weight_decay}')
+        self.clip_norm = _clip_value(clip_norm)
+        self._trust = bool(trust)
+        super().__init__(params, lr, betas, eps, weight_decay, 1.0, capturable)
+        self.defaults['trust'] = self._trust
+        error = 'FusedLAMB: run at least one eager step() (capturable=True) and begin_capture() before capturing a graph'
+        self._tables = {0: WordTable(error, capturable)}          # [6][n], see _table; FusedAdam's begin_capture / load_state_dict serve it
+        self._chunks = WordTable(error)
+        self._work = _TrustWorkspace('FusedLAMB')
+        self._hyper = None        # (host values, device double [G][6])
+        self._clip_out = None     # device float [2]: norm, coefficient
+
+    def add_param_group(self, group):
+        super().add_param_group(group)
+        self.param_groups[-1].setdefault('trust', self._trust)
+
+    def load_state_dict(self, state_dict):
+        kept = [g['trust'] for g in self.param_groups]
+        super().load_state_dict(state_dict)
+        for g, t in zip(self.param_groups, kept):
+            g.setdefault('trust', t)
+        steps = [self._step_of(p) for p, st in self.state.items() if st]
+        if steps and 0 in self._dev:
+            self._dev[0]['state'][0] = float(max(steps))
+
+    @property
+    def last_grad_norm(self):
+        """fp32 device scalar of the global gradient norm of the last clipped step (None before one)."""
+        return None if self._clip_out is None else self._clip_out[0]
+
+    @property
+    def last_trust_ratio(self):
+        return self._work.ratio
+
+    def _sync_hyper(self, dev):
+        vals = tuple(float(v) for g in self.param_groups for v in (g['lr'], g['betas'][0], g['betas'][1], g['eps'], g['weight_decay'],
+                                                                   1.0 if g['trust'] else 0.0))
+        self._hyper = _refresh_hyper('FusedLAMB', self._hyper, vals, dev)
+
+    def sync_lr(self):
+        """Refresh the device hyper-parameter table from param_groups, as ``FusedSGD.sync_lr``."""
+        if self._hyper is not None:
+            self._sync_hyper(self._hyper[1].device)
+
+    def _table(self):
+        """(parameters that have a gradient (all groups), their device table [6][n] = param | grad | exp_avg | size | group |
+        exp_avg_sq, chunk table), each table rebuilt only when its words changed."""
+        ps, gids = [], []
+        for gi, group in enumerate(self.param_groups):
+            for p in group['params']:
+                if p.grad is None:
+                    continue
+                if not p.is_cuda:
+                    raise RuntimeError('FusedLAMB: parameters must live on the GPU (no CPU path)')
+                if p.dtype != torch.float32 or p.grad.dtype != torch.float32 or not p.is_contiguous() or not p.grad.is_contiguous():
+                    raise RuntimeError('FusedLAMB needs contiguous fp32 parameters and gradients')
+                if p.grad.is_sparse:
+                    raise RuntimeError('FusedLAMB does not support sparse gradients')
+                st = self.state[p]
+                if not st:
+                    if capturing(p.device):
+                        raise RuntimeError(self._tables[0].capture_error)
+                    st['step'] = 0
+                    st['exp_avg'] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+                    st['exp_avg_sq'] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+                ps.append(p)
+                gids.append(gi)
+        if not ps:
+            return None
+        dev = ps[0].device
+        sizes = tuple(p.numel() for p in ps)
+        key = (tuple(p.data_ptr() for p in ps), tuple(p.grad.data_ptr() for p in ps), tuple(self.state[p]['exp_avg'].data_ptr() for p in ps),
+               sizes, tuple(gids), tuple(self.state[p]['exp_avg_sq'].data_ptr() for p in ps))
+        chunks = self._chunks.get(sizes, lambda: chunk_words(chunks_of(s, _lib.call('fva_sgd_chunk_elems')) for s in sizes), dev)
+        return ps, self._tables[0].get(key, lambda: [w for row in key for w in row], dev), chunks
+
+    def _launch(self):
+        got = self._table()
+        if got is None:
+            return []
+        ps, tab, chunks = got
+        dev = ps[0].device
+        self._sync_hyper(dev)
+        first = self._work.first(tuple(p.numel() for p in ps), dev)
+        groups = len(self.param_groups)
+        d = self._dev.get(0)
+        if d is None or d['state'].numel() != 1 + 2 * groups:
+            if capturing(dev):
+                raise RuntimeError(self._tables[0].capture_error)
+            d = self._dev[0] = {'state': torch.zeros(1 + 2 * groups, dtype=torch.float64, device=dev), 'lr_host': None}
+            d['state'][0] = float(max(self._step_of(p) for p in ps))        # starts from the host step count: before it moves
+        if self.clip_norm is not None and self._clip_out is None:
+            if capturing(dev):
+                raise RuntimeError(self._tables[0].capture_error)
+            self._clip_out = torch.zeros(2, dtype=torch.float32, device=dev)
+        step = max(self._step_of(p) for p in ps) + 1
+        for p in ps:
+            self.state[p]['step'] = step
+        _lib.call('fva_lamb_step', _ptr(tab), len(ps), _ptr(chunks), chunks.numel(), _ptr(first), _ptr(self._hyper[1]), groups,
+                  _ptr(d['state']), self.clip_norm or 0.0, _ptr(self._work.partial), _ptr(self._work.ratio), _ptr(self._clip_out), _stream())
         return ps

@@ -576,6 +576,30 @@ int fva_sgd_step(const int64_t* tab_dev, int32_t n, const int64_t* chunks_dev, i
                  int32_t* fresh_dev, int32_t clear_fresh, const float* coef_dev, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Layer-wise adaptive optimizers (fastvision_amd.FusedLARS / FusedLAMB): every tensor's update is scaled by a trust ratio formed from
+ * the L2 norms of that tensor's weights and of its update.  Three passes over the chunk table of the SGD entry points (chunks of
+ * fva_sgd_chunk_elems() elements): per-chunk fp64 partial sums, one block per tensor for the ratio, the update.  Shared arguments:
+ *   tab_dev: int64 [6][n] = param | grad | momentum buffer (0: none; LARS) or exp_avg (LAMB) | element count | group index |
+ *            slot in fresh_dev (LARS) or exp_avg_sq (LAMB);
+ *   chunks_dev: int64 [nchunks] as for fva_sgd_step; first_dev: int64 [n + 1], the index of each tensor's first chunk, then nchunks;
+ *   hyper_dev: double [groups][7] = lr, weight_decay, momentum, 1 - dampening, nesterov, trust_coefficient, eps (LARS), or
+ *            double [groups][6] = lr, beta1, beta2, eps, weight_decay, trust (0 or 1) (LAMB), read at run time;
+ *   clip_norm: 0 for none, else the global-norm clip of fva_sgd_clip_coef with clip_out_dev[2] = {norm, coefficient} (may be NULL
+ *            without clipping); partial_dev: double [2][nchunks] scratch; ratio_dev: float [n], the trust ratio of every tensor.
+ * LARS: g = coef * grad; q = eta * |p| / (|g| + wd * |p| + eps) if eta, |p|, |g| > 0 else 1; g = q * (g + wd * p); then SGD's momentum,
+ * Nesterov and p -= lr * g, with fresh_dev / clear_fresh as in fva_sgd_step.  Clipping costs no extra pass over the gradients.
+ * LAMB: m, v as Adam from g = coef * grad; u = (m / (1 - beta1^t)) / (sqrt(v / (1 - beta2^t)) + eps) + wd * p; r = |p| / |u| if trust
+ * and |p|, |u| > 0 else 1; p -= lr * r * u.  state_dev: double [1 + 2 groups] = step count | 1 - beta1^t, 1 - beta2^t per group; the
+ * call first advances the count by one on the device (a captured step replays with the right corrections).
+ * Norms and ratios are fp64 in a fixed order (bit-identical runs); nothing is read back. */
+int fva_lars_step(const int64_t* tab_dev, int32_t n, const int64_t* chunks_dev, int32_t nchunks, const int64_t* first_dev,
+                  const double* hyper_dev, int32_t* fresh_dev, int32_t clear_fresh, double clip_norm, double* partial_dev,
+                  float* ratio_dev, float* clip_out_dev, void* stream);
+int fva_lamb_step(const int64_t* tab_dev, int32_t n, const int64_t* chunks_dev, int32_t nchunks, const int64_t* first_dev,
+                  const double* hyper_dev, int32_t groups, double* state_dev, double clip_norm, double* partial_dev,
+                  float* ratio_dev, float* clip_out_dev, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Exponential moving average of the weights (fastvision_amd.ModelEMA: the averaged model a YOLO trainer validates and checkpoints),
  * multi-tensor, counter and weight on the device (a captured training step replays it).  One call = one update:
  *   a one-thread tick computes, in double, k = state_dev[0] + 1, state_dev[0] = k, d = decay * (1 - exp(-k / tau)) (d = decay when
