@@ -5,7 +5,7 @@ Conv2d -> BatchNorm2d -> ReLU layer, its pieces, and the one max-pool node.
                                  fva_bn_eval_coeffs, the BatchNorm + ReLU apply pass; backward = the two BatchNorm + ReLU passes (training) or the
                                  one-pass frozen-statistics backward (ops.frozen_bn_bwd), then the convolution's weight and data gradients.
                                  The convolution is a back end: PlainConv (implicit GEMM on the packed weights, 1x1 / 3x3, stride 1 / 2) or
-                                 GroupedConv (fva_gconv_* on the fp32 master weight, or fva_gconv_mfma_* on its packed tables).  A convolution
+                                 GroupedConv (fva_gconv_* on the fp32 master weight, or fva_gconv_mfma_* / fva_gconv_mfma_s2_* on its packed tables).  A convolution
                                  bias (VGG) changes three launches and the dbias rule, see the node's docstring
     MaxPoolFn                    max_pool2 / max_pool3s2: two entry-point names and an output-size rule
     _conv_bn, _bn_relu_apply, _bn_relu_bwd, _bn_add_relu_bwd_identity, _block_bn_relu_bwd
@@ -162,6 +162,7 @@ class GroupedConv:
     'mfma':  where fva_gconv_mfma_serves(d) == 1 (bf16, stride 1, border 1, a map that fits the staging) the matrix-unit kernels:
              operands() launches fva_gconv_mfma_pack in front of every forward (not cached: a captured step replays it on the weights the
              optimizer has just written) and the forward / backward take the two packed tables; every other layer takes the plain launches.
+    'mfma_s2': 'mfma', and where fva_gconv_mfma_s2_serves(d) == 1 (bf16, stride 2, border 1) the same route through fva_gconv_mfma_s2_*.
     Its data gradient takes no addend: a tail's summand comes back through autograd."""
     k, fwd, blocks = 3, 'fva_gconv_fwd', 'fva_gconv_stat_blocks'
     wgrad, wgrad_ws, dgrad = 'fva_gconv_wgrad', 'fva_gconv_wgrad_workspace', 'fva_gconv_dgrad'
@@ -175,14 +176,18 @@ class GroupedConv:
             w = w.float().contiguous()
         d = _lib.GConvDesc(code, B, H, W, Cin, self.groups, self.stride, x_pad, 1)
         lib = _lib.load()
-        if self.path != 'mfma' or lib.fva_gconv_mfma_serves(C.byref(d)) != 1:
+        if self.path in ('mfma', 'mfma_s2') and lib.fva_gconv_mfma_serves(C.byref(d)) == 1:
+            pre = 'fva_gconv_mfma_'
+        elif self.path == 'mfma_s2' and lib.fva_gconv_mfma_s2_serves(C.byref(d)) == 1:
+            pre = 'fva_gconv_mfma_s2_'
+        else:
             return d, w, w
-        self.fwd, self.blocks = 'fva_gconv_mfma_fwd', 'fva_gconv_mfma_stat_blocks'
-        self.wgrad, self.wgrad_ws, self.dgrad = 'fva_gconv_mfma_wgrad', 'fva_gconv_mfma_wgrad_workspace', 'fva_gconv_mfma_dgrad'
-        nb = lib.fva_gconv_mfma_pack_bytes(C.byref(d))
+        self.fwd, self.blocks = pre + 'fwd', pre + 'stat_blocks'
+        self.wgrad, self.wgrad_ws, self.dgrad = pre + 'wgrad', pre + 'wgrad_workspace', pre + 'dgrad'
+        nb = getattr(lib, pre + 'pack_bytes')(C.byref(d))
         wf = torch.empty(nb, dtype=torch.uint8, device=w.device)
         wb = torch.empty_like(wf)
-        _lib.call('fva_gconv_mfma_pack', C.byref(d), _p(w), _p(wf), _p(wb), _stream())
+        _lib.call(pre + 'pack', C.byref(d), _p(w), _p(wf), _p(wb), _stream())
         return d, wf, wb
 
     def backward(self, d, x_ptr, dy, w, wshape, keep, weight, need_x, need_w, addend):

@@ -29,28 +29,12 @@
 // slots; the K index of the weight gradient is permuted for that (the same permutation on both operands).  Everything fits the default
 // 64 KB; a map too wide for that is not served (fva_gconv_mfma_serves).
 // No atomics, fixed order everywhere: the same bits on every run.
-#include <type_traits>
-
-#include "common.h"
+#include "grouped_mfma_common.h"
 
 namespace {
 
 constexpr int RUN = 256;       // positions per block, forward and data gradient = rows of one statistics block
 constexpr int WRUN = 128;      // positions per staged run of the weight gradient
-constexpr int CH = 64;         // channels per block
-constexpr int PITCH = 160;     // bytes per staged position (128 of data)
-constexpr int LDS_MAX = 64 * 1024;
-
-constexpr int steps_of(int cg) { return cg >= 32 ? 9 * (cg / 32) : 5; }
-
-using lds_s16x4 = __attribute__((address_space(3))) s16x4;
-using s16x8 = __attribute__((ext_vector_type(8))) short;
-
-__device__ __forceinline__ bf16x8 tr_pair(const char* lo, const char* hi) {
-    const s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)lo);
-    const s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)hi);
-    return __builtin_bit_cast(bf16x8, (s16x8)__builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7));
-}
 
 // ------------------------------------------------------------------------------------------------ pack
 template <int CG>
@@ -293,30 +277,6 @@ __global__ __launch_bounds__(256) void gconv_mfma_wgrad_kernel(const bf16_t* __r
     }
 }
 
-// The splits are many and the elements few at the wide maps (1682 splits of 4608 elements at C = 128, Cg = 4, 56^2): one thread per element
-// walking all its splits is a chain of that many dependent-latency loads on a handful of blocks.  So 16 threads share an element: each adds
-// a contiguous sixteenth of the splits in their order, and the sixteen sums are added in their order -- still one fixed order.
-constexpr int RED_E = 16, RED_S = 16;      // elements per block x slices of the splits
-__global__ __launch_bounds__(RED_E * RED_S) void gconv_mfma_wgrad_reduce_kernel(const float* __restrict__ partial, float* __restrict__ dw, int n,
-                                                                                int splits) {
-    __shared__ double part[RED_S][RED_E];
-    const int e = threadIdx.x % RED_E, sl = threadIdx.x / RED_E;
-    const int i = blockIdx.x * RED_E + e;
-    const int per = (splits + RED_S - 1) / RED_S;
-    const int j0 = sl * per, j1 = min(splits, j0 + per);
-    double s = 0.0;
-    if (i < n)
-        for (int j = j0; j < j1; ++j) s += (double)partial[(int64_t)j * n + i];
-    part[sl][e] = s;
-    __syncthreads();
-    if (sl == 0 && i < n) {
-        double t = 0.0;
-#pragma unroll
-        for (int k = 0; k < RED_S; ++k) t += part[k][e];
-        dw[i] = (float)t;
-    }
-}
-
 // ------------------------------------------------------------------------------------------------ host
 const char* const CONTRACT =
     "the MFMA path serves FVA_BF16 at stride 1 with in_pad == dy_pad == 1, C % 64 == 0, C <= 2048, C = groups * Cg, Cg in {4, 8, 16, 32, 64}, "
@@ -340,17 +300,6 @@ int refuse(const char* who, const fva_gconv_desc* d) {
                     d->H, d->W, d->C, d->groups, d->stride, d->in_pad, d->dy_pad);
 }
 
-template <typename F>
-void by_cg(int cg, F&& f) {
-    switch (cg) {
-        case 4: f(std::integral_constant<int, 4>{}); break;
-        case 8: f(std::integral_constant<int, 8>{}); break;
-        case 16: f(std::integral_constant<int, 16>{}); break;
-        case 32: f(std::integral_constant<int, 32>{}); break;
-        default: f(std::integral_constant<int, 64>{}); break;
-    }
-}
-
 int64_t total_of(const fva_gconv_desc* d) { return (int64_t)d->B * (d->H + 2) * (d->W + 2); }
 
 int64_t pack_elems(const fva_gconv_desc* d) { return (int64_t)(d->C / 16) * steps_of(d->C / d->groups) * 512; }
@@ -368,22 +317,7 @@ int launch_gather(const char* who, const fva_gconv_desc* d, const void* src, con
     return FVA_OK;
 }
 
-struct WPlan {
-    int nruns, splits, runs_per_split;
-};
-WPlan wgrad_plan(const fva_gconv_desc* d) {
-    WPlan p;
-    p.nruns = cdiv(total_of(d), WRUN);
-    const int64_t one = (int64_t)d->C * (d->C / d->groups) * 9 * 4;
-    int64_t want = 4096 / (d->C / CH);                                             // blocks in flight: a few per CU
-    const int64_t cap = (64ll << 20) / one > 0 ? (64ll << 20) / one : 1;           // at most 64 MB of partials
-    if (want > cap) want = cap;
-    if (want > p.nruns) want = p.nruns;
-    if (want < 1) want = 1;
-    p.runs_per_split = cdiv(p.nruns, want);
-    p.splits = cdiv(p.nruns, p.runs_per_split);
-    return p;
-}
+WPlan wgrad_plan(const fva_gconv_desc* d) { return wgrad_plan_of(cdiv(total_of(d), WRUN), d->C, d->C / d->groups); }
 
 }  // namespace
 
@@ -442,9 +376,7 @@ int fva_gconv_mfma_wgrad(const fva_gconv_desc* d, const void* x, const void* dy,
                            (float*)ws, g);
     });
     FVA_LAUNCH_CHECK("gconv_mfma_wgrad_kernel");
-    hipLaunchKernelGGL(gconv_mfma_wgrad_reduce_kernel, dim3(cdiv(n, RED_E)), dim3(RED_E * RED_S), 0, (hipStream_t)stream, (const float*)ws, dw_oihw, n, p.splits);
-    FVA_LAUNCH_CHECK("gconv_mfma_wgrad_reduce_kernel");
-    return FVA_OK;
+    return launch_wgrad_reduce(ws, dw_oihw, n, p.splits, stream);
 }
 
 }  // extern "C"

@@ -7,7 +7,7 @@
     conv_bn_relu(x, conv, bn)        bias-free Conv2d (1x1 s1, 3x3 s1, 3x3 s2) -> BatchNorm2d -> ReLU: conv_bn_ops.ConvBNReLUFn, the node that
                                      vgg_ops.conv_bn_relu runs too, without a bias; frozen statistics take the one-pass backward.  A grouped
                                      3x3 (ResNeXt's conv2; GROUPED_CONTRACT) is the same node on conv_bn_ops.GroupedConv (fva_gconv_*, or
-                                     fva_gconv_mfma_* under set_grouped_path('mfma'))
+                                     fva_gconv_mfma_* / fva_gconv_mfma_s2_* under set_grouped_path('mfma' / 'mfma_s2'))
     conv_bn_add_relu(x, conv, bn, identity)
     conv_bn_add_relu(x, conv, bn, shortcut_in, shortcut_conv, shortcut_bn)
                                      the tail of a residual block, relu(bn(conv(x)) + R) with the add INSIDE the ReLU, one autograd node:
@@ -140,20 +140,20 @@ GROUPED_CONTRACT = ('conv_bn_relu: a grouped convolution is on this path as a 3x
 
 # Which kernels a grouped 3x3 takes.  'plain' (the default): the FMA kernels of grouped.hip at every layer, the launches every recorded
 # sequence and every earlier measurement were made with.  'mfma': the matrix-unit kernels of grouped_mfma.hip at the layers they serve (bf16,
-# stride 1); stride 2 and fp32 stay plain.  The default moves only once the measured table of DESIGN 3.12 says it should.
+# stride 1); stride 2 and fp32 stay plain.  'mfma_s2': 'mfma', and the kernels of grouped_mfma_s2.hip at the bf16 stride-2 layers.  The default moves only once the measured table of DESIGN 3.12 says it should.
 _GROUPED = {'path': 'plain'}
 
 
 def set_grouped_path(mode):
-    """'plain' | 'mfma' (see above).  Returns the previous mode."""
-    if mode not in ('plain', 'mfma'):
-        raise ValueError("grouped path must be 'plain' or 'mfma'")
+    """'plain' | 'mfma' | 'mfma_s2' (see above).  Returns the previous mode."""
+    if mode not in ('plain', 'mfma', 'mfma_s2'):
+        raise ValueError("grouped path must be 'plain' or 'mfma' or 'mfma_s2'")
     prev, _GROUPED['path'] = _GROUPED['path'], mode
     return prev
 
 
 def get_grouped_path():
-    """The path in force for grouped 3x3 layers: 'plain' or 'mfma'."""
+    """The path in force for grouped 3x3 layers: 'plain', 'mfma' or 'mfma_s2'."""
     return _GROUPED['path']
 
 

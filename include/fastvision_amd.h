@@ -883,6 +883,38 @@ int     fva_gconv_mfma_dgrad(const fva_gconv_desc*, const void* dy, const void* 
 int64_t fva_gconv_mfma_wgrad_workspace(const fva_gconv_desc*);
 int     fva_gconv_mfma_wgrad(const fva_gconv_desc*, const void* x, const void* dy, float* dw_oihw, void* ws, int64_t ws_bytes, void* stream);
 
+/* ---- The stride-2 layers on the matrix units (grouped_mfma_s2.hip; version 13) ------------------------------------------------------------
+ * The sibling of fva_gconv_mfma_* for stride 2 (the first conv2 of res3, res4 and res5): dtype FVA_BF16, stride 2, in_pad == dy_pad == 1, the
+ * C / Cg contract above, any H, W >= 1 (even or odd; OH = (H - 1) / 2 + 1), B (H + 2)(W + 2) < 2^31, and a map whose staging fits 64 KB of
+ * LDS (W <= 84).  Same argument lists, same rules: fva_gconv_mfma_s2_serves answers 1 / 0 (pure host, sets no error); every other entry
+ * refuses a descriptor it answers 0 for with FVA_ERR_ARG and a message naming this contract and launches nothing; the size functions return
+ * 0.  Tensors as above: x halo [B][H + 2][W + 2][C], y dense [B OH OW][C], dy halo [B][OH + 2][OW + 2][C] (zero border), dx dense
+ * [B][H][W][C], dw fp32 [C][Cg][3][3].  fva_gconv_mfma_* and fva_gconv_mfma_s2_* serve disjoint descriptors.
+ *   fva_gconv_mfma_s2_pack: as fva_gconv_mfma_pack, two tables of fva_gconv_mfma_s2_pack_bytes(d) bytes each, [C / 16][steps][64][8], lane l,
+ *   element j = row m = l % 16 (channel c = 16 slab + m), k = 8 (l / 16) + j.  The FORWARD table is the stride-1 forward table.  The
+ *   DATA-GRADIENT table is in CLASS order: a dx pixel (2 i + py, 2 j + px) meets the taps of its parity class only, and the nine taps
+ *   3 kh + kw are laid out as slots 0 ... 8 = 4 | 3 5 | 1 7 | 0 2 6 8 (classes (py, px) = (0,0) | (0,1) | (1,0) | (1,1)); tap (kh, kw) reads
+ *   dy-halo position (b, i + 1 + (kh == 0), j + 1 + (kw == 0)).  Not flipped: slot s holds w[..][..][tap(s)].
+ *     Cg >= 32: steps = 9 Cg / 32, step = slot * (Cg / 32) + h, partner kc = 32 h + k of c's group (first channel gb):
+ *               w[gb + kc][c - gb][tap(slot)].  Class (py, px) owns the steps of its slots.
+ *     Cg <= 16: steps = 5, slot = 2 step + k / 16 - 1 (slot -1, the first half-step, is zero), partner kc = k % 16 of the slab, zero unless
+ *               kc / Cg == m / Cg: w[16 slab + kc][m % Cg][tap(slot)].  Classes own steps 0 | 1 | 2 | 3 4.
+ *   fva_gconv_mfma_s2_fwd: stats_partial [fva_bn_partial_rows(fva_gconv_mfma_s2_stat_blocks(d))][2][C]: one row per block of 64 consecutive
+ *   PLANE positions T = (b (OH + 1) + i)(OW + 1) + j, the sums of y and y^2 over the block's real outputs (i < OH, j < OW) from the
+ *   unrounded accumulators; fva_bn_finalize takes it unchanged with count = B OH OW.  NULL: no statistics (eval mode).
+ *   fva_gconv_mfma_s2_dgrad: writes every dx element exactly once.
+ *   fva_gconv_mfma_s2_wgrad: workspace of fva_gconv_mfma_s2_wgrad_workspace(d) bytes; FVA_ERR_WORKSPACE if short.
+ * Arithmetic as fva_gconv_mfma_*, with its remarks on non-finite inputs; the weight gradient sums over the plane positions, where dy's zero
+ * border (read at i = OH and j = OW) adds exact zeros. */
+int     fva_gconv_mfma_s2_serves(const fva_gconv_desc*);
+int64_t fva_gconv_mfma_s2_pack_bytes(const fva_gconv_desc*);
+int     fva_gconv_mfma_s2_pack(const fva_gconv_desc*, const float* w_oihw, void* wpack_fwd, void* wpack_dgrad, void* stream);
+int32_t fva_gconv_mfma_s2_stat_blocks(const fva_gconv_desc*);
+int     fva_gconv_mfma_s2_fwd(const fva_gconv_desc*, const void* x, const void* wpack_fwd, void* y, float* stats_partial, void* stream);
+int     fva_gconv_mfma_s2_dgrad(const fva_gconv_desc*, const void* dy, const void* wpack_dgrad, void* dx, void* stream);
+int64_t fva_gconv_mfma_s2_wgrad_workspace(const fva_gconv_desc*);
+int     fva_gconv_mfma_s2_wgrad(const fva_gconv_desc*, const void* x, const void* dy, float* dw_oihw, void* ws, int64_t ws_bytes, void* stream);
+
 /* ---- Label smoothing, MixUp and CutMix (not in the reference: the standard recipe of its classifiers; version 12) -------------------
  * fva_mix_plan: a ONE-THREAD tick kernel that decides, on the device, what the next batch gets.  state = int64[4] in DEVICE memory,
  * {seed, call counter, 0, 0} (the protocol of fva_dropout_fwd): the launch reads seed and counter and advances the counter itself, so a

@@ -6,17 +6,18 @@ Per model, on identically seeded weights (wall time over --steps steps after --w
     eager     the library step
     torch     the same network from stock torch.nn modules on the same GPU (bf16 autocast, channels_last, torch.optim.SGD)
 eager and torch ALTERNATE in one process, --rounds times each after warm-up; the figure per mode is the median of its rounds.  The eager
-step is taken once per grouped path of --grouped (resnet_ops.set_grouped_path: 'plain', the FMA kernels of csrc/grouped.hip, and 'mfma',
-the matrix-unit kernels of csrc/grouped_mfma.hip at the stride-1 layers), all in the same alternation; every figure carries a ``grouped`` key.
+step is taken once per grouped path of --grouped (resnet_ops.set_grouped_path: 'plain', the FMA kernels of csrc/grouped.hip, 'mfma', the
+matrix-unit kernels of csrc/grouped_mfma.hip at the stride-1 layers, and 'mfma_s2', those and csrc/grouped_mfma_s2.hip at the stride-2
+layers), all in the same alternation; every figure carries a ``grouped`` key.
 
-Per grouped kernel (forward with statistics, data gradient, weight gradient; under 'mfma' also the pack launch that precedes every forward)
-at the six stride-1 shapes of DESIGN 3.12 and per path: device-event time over --iters launches after warm-up, the paths and a
+Per grouped kernel (forward with statistics, data gradient, weight gradient; on the matrix units also the pack launch that precedes every
+forward) at the six stride-1 shapes of DESIGN 3.12 ('plain' and 'mfma') and at the six stride-2 shapes ('plain' and 'mfma_s2'), per path: device-event time over --iters launches after warm-up, the paths and a
 device-to-device copy of x read + y written once (the floor's bytes) ALTERNATING --rounds times in one process; per figure the median, the
-best, and the spread between its rounds, the useful GFLOP, and under 'mfma' whether every round beat every round of 'plain'.
+best, and the spread between its rounds, the useful GFLOP, and on the matrix units whether every round beat every round of 'plain'.
 
 Writes one JSON object to --out (default profiles/bench_resnext.json) and prints it as one line.
 usage: python tools/bench_resnext.py [--steps K] [--warmup W] [--batch B] [--size S] [--rounds R] [--iters N] [--models a,b] [--modes eager,torch]
-[--grouped plain,mfma] [--no-kernels] [--out PATH]"""
+[--grouped plain,mfma,mfma_s2] [--no-kernels] [--out PATH]"""
 import argparse
 import ctypes as C
 import json
@@ -41,6 +42,9 @@ BLOCKS = {'resnext50_32x4d': ([3, 4, 6, 3], 32, 4), 'resnext101_32x8d': ([3, 4, 
 # (model, stage): C, Cg, map at 224 x 224 -- the stride-1 grouped layers of DESIGN 3.12's floor table
 SHAPES = [('50_32x4d res2', 128, 4, 56), ('50_32x4d res3', 256, 8, 28), ('50_32x4d res4', 512, 16, 14), ('50_32x4d res5', 1024, 32, 7),
           ('101_32x8d res2', 256, 8, 56), ('101_32x8d res5', 2048, 64, 7)]
+# the stride-2 grouped layers (the first conv2 of res3, res4, res5): C, Cg, INPUT map
+SHAPES_S2 = [('50_32x4d res3 s2', 256, 8, 56), ('50_32x4d res4 s2', 512, 16, 28), ('50_32x4d res5 s2', 1024, 32, 14),
+             ('101_32x8d res3 s2', 512, 16, 56), ('101_32x8d res4 s2', 1024, 32, 28), ('101_32x8d res5 s2', 2048, 64, 14)]
 
 
 def _cb(cin, cout, k, s=1, groups=1):
@@ -139,8 +143,8 @@ def bench_models(args, images, labels):
     return out
 
 
-ENTRY = {'plain': ('fva_gconv_fwd', 'fva_gconv_dgrad', 'fva_gconv_wgrad', 'fva_gconv_stat_blocks', 'fva_gconv_wgrad_workspace'),
-         'mfma': ('fva_gconv_mfma_fwd', 'fva_gconv_mfma_dgrad', 'fva_gconv_mfma_wgrad', 'fva_gconv_mfma_stat_blocks', 'fva_gconv_mfma_wgrad_workspace')}
+PREFIX = {'plain': 'fva_gconv_', 'mfma': 'fva_gconv_mfma_', 'mfma_s2': 'fva_gconv_mfma_s2_'}
+ENTRY = {g: tuple(pre + k for k in ('fwd', 'dgrad', 'wgrad', 'stat_blocks', 'wgrad_workspace')) for g, pre in PREFIX.items()}
 
 
 def _halo_randn(B, H, Cc, dt):
@@ -155,21 +159,22 @@ def bench_kernels(args):
     B, it, E = args.batch, args.iters, 2
     paths = args.grouped.split(',')
     rows = []
-    for tag, Cc, Cg, H in SHAPES:
+    for stride, (tag, Cc, Cg, H) in [(1, s) for s in SHAPES] + [(2, s) for s in SHAPES_S2]:
         H = H * args.size // 224
-        d = _lib.GConvDesc(code, B, H, H, Cc, Cc // Cg, 1, 1, 1)
-        M = B * H * H
-        x, dy = _halo_randn(B, H, Cc, dt), _halo_randn(B, H, Cc, dt)
+        OH = (H - 1) // stride + 1
+        d = _lib.GConvDesc(code, B, H, H, Cc, Cc // Cg, stride, 1, 1)
+        M = B * OH * OH
+        x, dy = _halo_randn(B, H, Cc, dt), _halo_randn(B, OH, Cc, dt)
         w = torch.randn(Cc, Cg, 3, 3, device=DEV) * (9 * Cg) ** -0.5
         y = torch.empty((M, Cc), dtype=dt, device=DEV)
         dx = torch.empty((B, H, H, Cc), dtype=dt, device=DEV)
         dw = torch.empty((Cc, Cg, 3, 3), dtype=torch.float32, device=DEV)
-        nbytes, gflop = 2 * M * Cc * E, 2.0 * M * Cc * Cg * 9 / 1e9
+        nbytes, gflop = (B * H * H + M) * Cc * E, 2.0 * M * Cc * Cg * 9 / 1e9
         src = torch.empty(nbytes // 2, dtype=torch.uint8, device=DEV)
         dst = torch.empty_like(src)
         fns, keep = {}, []
         for g in paths:
-            if g == 'mfma' and lib.fva_gconv_mfma_serves(C.byref(d)) != 1:
+            if g != 'plain' and getattr(lib, PREFIX[g] + 'serves')(C.byref(d)) != 1:
                 continue
             fwd, dgrad, wgrad, blocks, wsf = ENTRY[g]
             nblk = getattr(lib, blocks)(C.byref(d))
@@ -177,11 +182,12 @@ def bench_kernels(args):
             wsb = getattr(lib, wsf)(C.byref(d))
             ws = torch.empty(wsb, dtype=torch.uint8, device=DEV)
             wf = wb = w
-            if g == 'mfma':
-                nb = lib.fva_gconv_mfma_pack_bytes(C.byref(d))
+            if g != 'plain':
+                pack = PREFIX[g] + 'pack'
+                nb = getattr(lib, pack + '_bytes')(C.byref(d))
                 wf, wb = torch.empty(nb, dtype=torch.uint8, device=DEV), torch.empty(nb, dtype=torch.uint8, device=DEV)
-                fns[(g, 'fva_gconv_mfma_pack')] = lambda wf=wf, wb=wb: _lib.call('fva_gconv_mfma_pack', C.byref(d), p(w), p(wf), p(wb), st())
-                fns[(g, 'fva_gconv_mfma_pack')]()
+                fns[(g, pack)] = lambda pack=pack, wf=wf, wb=wb: _lib.call(pack, C.byref(d), p(w), p(wf), p(wb), st())
+                fns[(g, pack)]()
             keep.append((stats, ws, wf, wb))
             fns[(g, fwd)] = lambda fwd=fwd, wf=wf, stats=stats: _lib.call(fwd, C.byref(d), p(x), p(wf), p(y), p(stats), st())
             fns[(g, dgrad)] = lambda dgrad=dgrad, wb=wb: _lib.call(dgrad, C.byref(d), p(dy), p(wb), p(dx), st())
@@ -195,12 +201,12 @@ def bench_kernels(args):
         cu = min(copy_us)
         for (g, name), v in us.items():
             med = statistics.median(v)
-            r = {'kernel': name, 'grouped': g, 'layer': tag, 'Cg': Cg, 'shape': [B, H, H, Cc], 'bytes': nbytes, 'us': round(med, 1),
+            r = {'kernel': name, 'grouped': g, 'layer': tag, 'Cg': Cg, 'stride': stride, 'shape': [B, H, H, Cc], 'bytes': nbytes, 'us': round(med, 1),
                  'us_best': round(min(v), 1), 'us_rounds': [round(t, 1) for t in v], 'spread': round((max(v) - min(v)) / med, 4),
                  'gb_per_s': round(nbytes / med / 1e3, 1), 'copy_us': round(cu, 1), 'copy_gb_per_s': round(nbytes / cu / 1e3, 1),
                  'share_of_copy_rate': round(cu / med, 3), 'useful_gflop': round(gflop, 2), 'useful_tflop_per_s': round(gflop / med * 1e3, 2),
                  'hbm_floor_us_at_5p5_tb_per_s': round(nbytes / 5.5e6, 1)}
-            twin = ENTRY['plain'][ENTRY['mfma'].index(name)] if g == 'mfma' and name in ENTRY['mfma'] else None
+            twin = ENTRY['plain'][ENTRY[g].index(name)] if g != 'plain' and name in ENTRY[g] else None
             if twin is not None and ('plain', twin) in us:
                 r['plain_us'] = round(statistics.median(us[('plain', twin)]), 1)
                 r['beats_plain_in_every_round'] = max(v) < min(us[('plain', twin)])      # by more than the spread between rounds of a mode
@@ -232,10 +238,11 @@ def main():
            'steps': args.steps, 'warmup': args.warmup, 'rounds': args.rounds, 'device': torch.cuda.get_device_name(0),
            'reference': 'torch: the same network from stock torch.nn on the same device, bf16 autocast, channels_last, torch.optim.SGD',
            'grouped_paths': {'plain': 'the FMA kernels of csrc/grouped.hip at every grouped layer (the default of resnet_ops)',
-                             'mfma': 'the matrix-unit kernels of csrc/grouped_mfma.hip at the bf16 stride-1 layers, plain elsewhere'}}
+                             'mfma': 'the matrix-unit kernels of csrc/grouped_mfma.hip at the bf16 stride-1 layers, plain elsewhere',
+                             'mfma_s2': 'mfma, and the kernels of csrc/grouped_mfma_s2.hip at the bf16 stride-2 layers'}}
     for g in args.grouped.split(','):
         if g not in ENTRY:
-            raise SystemExit(f'bench_resnext: --grouped takes plain and mfma, got {g}')
+            raise SystemExit(f'bench_resnext: --grouped takes plain, mfma and mfma_s2, got {g}')
     with fastvision_amd.compute_dtype(torch.bfloat16):
         out.update(bench_models(args, images, labels))
         if not args.no_kernels:
