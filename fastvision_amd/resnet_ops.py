@@ -140,7 +140,7 @@ GROUPED_CONTRACT = ('conv_bn_relu: a grouped convolution is on this path as a 3x
 
 # Which kernels a grouped 3x3 takes.  'plain' (the default): the FMA kernels of grouped.hip at every layer, the launches every recorded
 # sequence and every earlier measurement were made with.  'mfma': the matrix-unit kernels of grouped_mfma.hip at the layers they serve (bf16,
-# stride 1); stride 2 and fp32 stay plain.  'mfma_s2': 'mfma', and the kernels of grouped_mfma_s2.hip at the bf16 stride-2 layers.  The default moves only once the measured table of DESIGN 3.12 says it should.
+# stride 1); stride 2 and fp32 stay plain.  'mfma_s2': 'mfma', and the kernels of grouped_mfma.hip at the bf16 stride-2 layers.  The default moves only once the measured table of DESIGN 3.12 says it should.
 _GROUPED = {'path': 'plain'}
 
 

@@ -883,7 +883,7 @@ int     fva_gconv_mfma_dgrad(const fva_gconv_desc*, const void* dy, const void* 
 int64_t fva_gconv_mfma_wgrad_workspace(const fva_gconv_desc*);
 int     fva_gconv_mfma_wgrad(const fva_gconv_desc*, const void* x, const void* dy, float* dw_oihw, void* ws, int64_t ws_bytes, void* stream);
 
-/* ---- The stride-2 layers on the matrix units (grouped_mfma_s2.hip; version 13) ------------------------------------------------------------
+/* ---- The stride-2 layers on the matrix units (grouped_mfma.hip; version 13) ---------------------------------------------------------------
  * The sibling of fva_gconv_mfma_* for stride 2 (the first conv2 of res3, res4 and res5): dtype FVA_BF16, stride 2, in_pad == dy_pad == 1, the
  * C / Cg contract above, any H, W >= 1 (even or odd; OH = (H - 1) / 2 + 1), B (H + 2)(W + 2) < 2^31, and a map whose staging fits 64 KB of
  * LDS (W <= 84).  Same argument lists, same rules: fva_gconv_mfma_s2_serves answers 1 / 0 (pure host, sets no error); every other entry

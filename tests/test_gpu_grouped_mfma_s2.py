@@ -5,7 +5,7 @@ must give identical bits, the statistics table is folded by the real fva_bn_fina
 with the stride-2 term counts (derived, not observed): y and dx half a bf16 ulp of the reference plus sum_limit(9 Cg, S), dw
 sum_limit(B OH OW, S['dw']), statistics gm.stat_limits with RUN = 64, the plane positions per block of the stride-2 forward.
 
-The kernels' tiles (csrc/grouped_mfma_s2.hip): forward -- runs of 64 plane positions over [B][OH + 1][OW + 1]; data gradient -- runs of 128
+The kernels' tiles (csrc/grouped_mfma.hip): forward -- runs of 64 plane positions over [B][OH + 1][OW + 1]; data gradient -- runs of 128
 dy-halo positions over [B][OH + 2][OW + 2]; weight gradient -- runs of 64 plane positions."""
 import ctypes as C
 

@@ -7,7 +7,7 @@ Per model, on identically seeded weights (wall time over --steps steps after --w
     torch     the same network from stock torch.nn modules on the same GPU (bf16 autocast, channels_last, torch.optim.SGD)
 eager and torch ALTERNATE in one process, --rounds times each after warm-up; the figure per mode is the median of its rounds.  The eager
 step is taken once per grouped path of --grouped (resnet_ops.set_grouped_path: 'plain', the FMA kernels of csrc/grouped.hip, 'mfma', the
-matrix-unit kernels of csrc/grouped_mfma.hip at the stride-1 layers, and 'mfma_s2', those and csrc/grouped_mfma_s2.hip at the stride-2
+matrix-unit kernels of csrc/grouped_mfma.hip at the stride-1 layers, and 'mfma_s2', those and the same file's at the stride-2
 layers), all in the same alternation; every figure carries a ``grouped`` key.
 
 Per grouped kernel (forward with statistics, data gradient, weight gradient; on the matrix units also the pack launch that precedes every
@@ -239,7 +239,7 @@ def main():
            'reference': 'torch: the same network from stock torch.nn on the same device, bf16 autocast, channels_last, torch.optim.SGD',
            'grouped_paths': {'plain': 'the FMA kernels of csrc/grouped.hip at every grouped layer (the default of resnet_ops)',
                              'mfma': 'the matrix-unit kernels of csrc/grouped_mfma.hip at the bf16 stride-1 layers, plain elsewhere',
-                             'mfma_s2': 'mfma, and the kernels of csrc/grouped_mfma_s2.hip at the bf16 stride-2 layers'}}
+                             'mfma_s2': 'mfma, and the kernels of csrc/grouped_mfma.hip at the bf16 stride-2 layers'}}
     for g in args.grouped.split(','):
         if g not in ENTRY:
             raise SystemExit(f'bench_resnext: --grouped takes plain, mfma and mfma_s2, got {g}')
