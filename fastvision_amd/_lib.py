@@ -276,6 +276,12 @@ PROTOTYPES = {
     'fva_mix_apply': (_I, [_I, _P, _P, _P, _I, _I, _I, _I, _P]),
     'fva_softmax_ce_soft': (_I, [_P, _P, _I, _P, _P, _I, _I, _I, _F, _P, _P, _P, _P, _P]),
     'fva_topk_accuracy': (_I, [_P, _I, _P, _I, _I, _I, _I, _P, _P, _P]),
+    'fva_randaug_plan': (_I, [_P, _I, _I, _I, _I, _I, _I, C.c_uint32, _P, _P]),
+    'fva_randaug_plan_fixed': (_I, [_P, _P, _I, _I, _P, _P]),
+    'fva_randaug_workspace': (_L, [_I]),
+    'fva_randaug_stats': (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P]),
+    'fva_randaug_apply': (_I, [_P, _P, _P, _I, _I, _I, _I, _I, C.c_uint32, _P, _P]),
+    'fva_random_erase': (_I, [_I, _P, _P, _P, _I, _I, _I, _I, _F, _F, _F, _F, _F, _I, _F, _P, _P]),
 }
 LABEL_I64, LABEL_F32 = 0, 1
 REDUCE_MEAN, REDUCE_SUM = 0, 1
@@ -283,7 +289,7 @@ UNCHECKED = {'fva_conv_patch_kernel', 'fva_sgd_chunk_elems', 'fva_ema_chunk_elem
              'fva_stem_stat_blocks', 'fva_stem_fused_blocks', 'fva_stem_wgrad_workspace', 'fva_stem_fwd_workspace', 'fva_stem_wgrad_mfma_workspace', 'fva_bn_bwd_blocks', 'fva_bn_partial_rows', 'fva_yolov3_loss_workspace',
              'fva_demo_loss_workspace', 'fva_demo_ciou_loss_workspace', 'fva_nms_candidates_workspace', 'fva_nms_select_workspace', 'fva_softmax_ce_workspace', 'fva_bn_frozen_bwd_blocks', 'fva_stem7_kp', 'fva_bn_add_relu_bwd_blocks', 'fva_gconv_stat_blocks', 'fva_gconv_wgrad_workspace',
              'fva_gconv_mfma_serves', 'fva_gconv_mfma_pack_bytes', 'fva_gconv_mfma_stat_blocks', 'fva_gconv_mfma_wgrad_workspace',
-             'fva_gconv_mfma_s2_serves', 'fva_gconv_mfma_s2_pack_bytes', 'fva_gconv_mfma_s2_stat_blocks', 'fva_gconv_mfma_s2_wgrad_workspace'}
+             'fva_gconv_mfma_s2_serves', 'fva_gconv_mfma_s2_pack_bytes', 'fva_gconv_mfma_s2_stat_blocks', 'fva_gconv_mfma_s2_wgrad_workspace', 'fva_randaug_workspace'}
 
 _lib = None
 

@@ -18,12 +18,14 @@ HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 LIB = os.path.join(HERE, 'libfastvision_amd.so')
 SOURCES = ['errors.hip', 'conv_igemm.hip', 'conv_wgrad.hip', 'bn_act.hip', 'stem.hip', 'head.hip', 'loss.hip',
            'optim.hip', 'ema.hip', 'detect.hip', 'pipeline.hip', 'colour.hip', 'roi.hip', 'vgg.hip', 'classify.hip', 'resnet.hip', 'grouped.hip',
-           'grouped_mfma.hip', 'mix.hip', 'soft_ce.hip', 'layerwise.hip']
+           'grouped_mfma.hip', 'mix.hip', 'soft_ce.hip', 'layerwise.hip', 'randaug.hip']
 # -ffp-contract=off: the matcher must reproduce the reference's fp32 op order bit for bit (no FMA fusion)
 FLAGS = ['--offload-arch=gfx950', '-O3', '-fPIC', '-std=c++17', '-Wall', '-Wno-unused-function'] + os.environ.get('FVA_EXTRA_FLAGS', '').split()   # experiments: e.g. -DFVA_NT_STORES=1 (use with --force)
 PER_FILE = {'colour.hip': ['-ffp-contract=off'], 'loss.hip': ['-ffp-contract=off'], 'detect.hip': ['-ffp-contract=off'], 'roi.hip': ['-ffp-contract=off'],
             # scalar fp32 arithmetic only: the norm and apply passes of LAMB must round the update direction alike
-            'layerwise.hip': ['-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops']}
+            'layerwise.hip': ['-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops'],
+            # the op arithmetic of RandAugment is a stated fp32 sequence: no FMA fusion, scalar fp32 only
+            'randaug.hip': ['-ffp-contract=off', '-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops']}
 
 
 def _newer(src, obj):

@@ -969,6 +969,70 @@ int fva_softmax_ce_soft(const float* logits, const void* labels, int label_dtype
 int fva_topk_accuracy(const void* logits, int logits_dtype, const void* labels, int label_dtype, int32_t R, int32_t C, int32_t k, float* out,
                       void* workspace, void* stream);
 
+/* ---- RandAugment and RandomErasing (not in the reference: per-image augmentation of its classifiers' recipe; version 14) --------------
+ * uint8 canvases [B][H][W][3] (the output of fva_paste_resize_u8) in, the same out, op by op as torchvision's RandAugment space states them.
+ * Ops, in the order of the enum: v is the plan value, f = 1 + v, blend(x, d, f) = trunc(clamp(f x + (1 - f) d, 0, 255)), evaluated in fp32
+ * as d + f * (x - d) with each operation rounded on its own (x == d gives x: a flat region stays as it is); grey(p) =
+ * trunc(0.2989f r + 0.587f g + 0.114f b), summed left to right in fp32.
+ *   Identity      x
+ *   ShearX / Y    source = (x + v (y - cy), y) / (x, y + v (x - cx))            value at bin m of n: 0.3 m / (n - 1), signed
+ *   TranslateX/Y  source = (x - trunc(v), y) / (x, y - trunc(v)), integers      trunc(150 / 331 * W (or H) * m / (n - 1)), signed
+ *   Rotate        source = R(v) (p - c) + c, R = [[cos, -sin], [sin, cos]] of v degrees, x right and y down       30 m / (n - 1), signed
+ *   Brightness    blend(x, 0, f)                                                0.9 m / (n - 1), signed
+ *   Color         blend(x, grey(p), f)                                          same
+ *   Contrast      blend(x, mean of the image's grey bytes (exact sum / H W, rounded to fp32), f)                  same
+ *   Sharpness     blend(x, s, f), s = the 3 x 3 sum with weights [[1,1,1],[1,5,1],[1,1,1]] over 13 to nearest; the image's border pixels: x
+ *   Posterize     x & ~(2^(8 - v) - 1), v = bits                                8 - rint(m / ((n - 1) / 4))
+ *   Solarize      x >= v ? 255 - x : x                                          255 - 255 m / (n - 1)
+ *   AutoContrast  per channel, lo / hi = first / last non-zero bin: hi == lo: x, else ((x - lo) * 255) / (hi - lo) in integers
+ *   Equalize      per channel, step = (H W - count of the last non-zero bin) / 255 (integers): 0: x, else
+ *                 lut[i] = min(255, (cumsum[i - 1] + step / 2) / step), lut[0] = 0
+ * The geometric ops sample the NEAREST source pixel, floor(coordinate + 0.5) in fp32 about the centre c = ((W - 1) / 2, (H - 1) / 2); a
+ * source outside the image gives fill_rgb (r | g << 8 | b << 16).  The values are computed in double and rounded to fp32 once.
+ *
+ * fva_randaug_plan: a ONE-BLOCK tick kernel with the state protocol of fva_mix_plan (state = int64[4] {seed, call counter, 0, 0} in DEVICE
+ * memory, advanced by the launch).  Entry e = b * num_ops + round draws Philox block (e, 0, call counter lo, hi): word 0 picks the
+ * ((uint64(word) * enabled) >> 32)-th enabled op of op_mask (bit i = op i), bit 31 of word 1 negates the value of a signed op.
+ * plan: DEVICE [B][num_ops].  1 <= num_ops <= FVA_RANDAUG_MAX_OPS, 0 <= magnitude < num_bins, num_bins >= 2.
+ * fva_randaug_plan_fixed: the plan from DEVICE tables ops int32 [B][num_ops] and values float [B][num_ops]; an op out of range is Identity.
+ *
+ * One round r is fva_randaug_stats then fva_randaug_apply, ALTERNATING on one stream over one workspace of fva_randaug_workspace(B) bytes
+ * (16-byte aligned) that is ZERO before its first use and belongs to the library afterwards: it holds two sets of histograms int32
+ * [B][4][256] (R, G, B, grey) and the two words by which the launches agree on the set in use -- a stats launch adds into one set with
+ * integer atomics (deterministic) and returns the other, read by the apply launch before it, to zero; no clear launch, no host state.
+ * Images whose op of the round is not Contrast, AutoContrast or Equalize are not read by the stats launch.
+ * fva_randaug_apply: in -> out, never in place (ping-pong between two canvases over the rounds).  16-byte accesses when W % 16 == 0 and
+ * both canvases are 16-byte aligned, bytes otherwise.  B <= 65535, H, W <= 16384, H * W * 3 < 2^31.
+ *
+ * fva_random_erase: torchvision's RandomErasing on the planar batch [B][C][H][W] (FVA_F32 / FVA_BF16), x == out: in place (images that
+ * draw no box are not touched), else one pass into out.  Per image b, Philox block (b, 0, call): erase iff p >= 1 or u(word 0) < p; then up
+ * to 10 attempts a, block (b, 1 + a, call): area = H W (scale_lo + (scale_hi - scale_lo) u(word 0)), aspect = expf(log ratio_lo +
+ * (log ratio_hi - log ratio_lo) u(word 1)), h = rint(sqrtf(area * aspect)), w = rint(sqrtf(area / aspect)), accepted iff h < H and w < W,
+ * top = (uint64(word 2) * (H - h + 1)) >> 32, left likewise from word 3; no attempt accepted: no erase.  boxes: DEVICE int32 [B][4] =
+ * {top, left, h, w}, zeros for no erase.  The fill: `value`, or with noise != 0 N(0, 1) -- element e = (c H + y) W + x of image b takes
+ * Box-Muller on the pair (e & 3) >> 1 of block (e >> 2, 2^16 + b, call), cosine for even e and sine for odd -- rounded once to dtype.
+ * The state protocol is fva_randaug_plan's; a state is shared by no other entry point. */
+#define FVA_RANDAUG_NUM_OPS 14
+#define FVA_RANDAUG_MAX_OPS 4
+typedef enum {
+    FVA_RA_IDENTITY = 0, FVA_RA_SHEAR_X, FVA_RA_SHEAR_Y, FVA_RA_TRANSLATE_X, FVA_RA_TRANSLATE_Y, FVA_RA_ROTATE, FVA_RA_BRIGHTNESS, FVA_RA_COLOR,
+    FVA_RA_CONTRAST, FVA_RA_SHARPNESS, FVA_RA_POSTERIZE, FVA_RA_SOLARIZE, FVA_RA_AUTOCONTRAST, FVA_RA_EQUALIZE
+} fva_randaug_op;
+typedef struct {
+    int32_t op;                /* fva_randaug_op */
+    float value;
+} fva_randaug_op_t;
+int fva_randaug_plan(int64_t* state, int32_t B, int32_t num_ops, int32_t magnitude, int32_t num_bins, int32_t H, int32_t W, uint32_t op_mask,
+                     fva_randaug_op_t* plan, void* stream);
+int fva_randaug_plan_fixed(const int32_t* ops, const float* values, int32_t B, int32_t num_ops, fva_randaug_op_t* plan, void* stream);
+int64_t fva_randaug_workspace(int32_t B);
+int fva_randaug_stats(const uint8_t* canvases, const fva_randaug_op_t* plan, int32_t round, int32_t num_ops, int32_t B, int32_t H, int32_t W,
+                      int32_t* workspace, void* stream);
+int fva_randaug_apply(const uint8_t* in, uint8_t* out, const fva_randaug_op_t* plan, int32_t round, int32_t num_ops, int32_t B, int32_t H, int32_t W,
+                      uint32_t fill_rgb, int32_t* workspace, void* stream);
+int fva_random_erase(int dtype, const void* x, void* out, int64_t* state, int32_t B, int32_t C, int32_t H, int32_t W, float p, float scale_lo,
+                     float scale_hi, float ratio_lo, float ratio_hi, int32_t noise, float value, int32_t* boxes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
